@@ -28,6 +28,12 @@ sparse.rs:229). Inputs are resident in HBM before timing starts.
 
 value = B_alg / step time (whole job), with the canonical algorithmic bytes
 of SURVEY.md §8d: B_alg = 8(N+1) + 12 nnz + 8 n_cols k + 8 N k.
+
+A run sets up, warms up, times --steps steps and prints one JSON line
+(ms_per_step = the wall time of one timed step; the rooflines come from the
+library's HIP events of those same steps). --dump-outputs DIR writes the last
+step's output Csr for comparing two builds. --full adds the figures that take
+runs of their own: end_to_end_ms and cpu_baseline.
 """
 
 from __future__ import annotations
@@ -453,6 +459,47 @@ def verify_rows(m, x, k, dev, kind, ra, rb, full):
     return True, checked
 
 
+DUMP_SEED = 1002
+DUMP_BUDGET = 48 << 20  # bytes of .npy data per dump
+
+
+def dump_outputs(path, out, k):
+    """Write the output Csr `out` (a device handle: what Csr::mul_dense
+    returns) as path/<name>.npy. A row of it holds at most k entries, so the
+    number of rows that fit DUMP_BUDGET follows from the shape alone: every
+    row when they all fit, else a sorted sample drawn with DUMP_SEED, the same
+    rows in every run of a config.
+      shape.npy      f64 [rows, cols, nnz] of the whole output
+      rows.npy       f64 indices of the dumped rows
+      row_ptr.npy    f64 offsets of the dumped rows in the two files below
+      col_index.npy  f64 column of every entry of the dumped rows
+      values.npy     the entries, f32 or f64 as computed"""
+    rp, ci, v = out.download()
+    rows = int(out.rows)
+    vdt = np.float32 if v.dtype == np.float32 else np.float64
+    per_row = 16 + k * (8 + np.dtype(vdt).itemsize)
+    n = min(rows, DUMP_BUDGET // per_row)
+    if n == rows:
+        sel = np.arange(rows, dtype=np.int64)
+    else:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, n, replace=False)).astype(np.int64)
+    starts = rp[sel].astype(np.int64)
+    lens = rp[sel + 1].astype(np.int64) - starts
+    ptr = np.concatenate([[0], np.cumsum(lens)])
+    idx = np.repeat(starts - ptr[:-1], lens) + np.arange(ptr[-1], dtype=np.int64)
+    arrays = {
+        "shape": np.array([rows, out.cols, out.nnz], dtype=np.float64),
+        "rows": sel.astype(np.float64),
+        "row_ptr": ptr.astype(np.float64),
+        "col_index": ci[idx].astype(np.float64),
+        "values": v[idx].astype(vdt),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -461,7 +508,7 @@ def main():
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--dtype", default="f64", choices=("f64", "f32"),
                     help="value type of A, X and Y (BASELINE's configs are f64; f32 = the generic-T path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-rows", type=int, default=100_000,
                     help="rows of the CPU baseline sample (configs with more rows are extrapolated)")
     ap.add_argument("--panel-cols", type=int, default=None,
@@ -483,10 +530,19 @@ def main():
                          "bit (whole matrix up to 2e9 nnz, else the rows around every piece bound)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="PMC-measured HBM bytes per SpMM launch (from profiles/), reported as roofline.traffic")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host buffers in/out) figures")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the end-to-end (host buffers in/out) figures")
     ap.add_argument("--ref-benches", default=None,
                     help="comma list of the reference's own criterion benches to run instead "
                          "(sd_mul,ss_add,ss_mul; one JSON line per size)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the figures that take runs of their own: end_to_end_ms (unless "
+                         "--no-e2e) and cpu_baseline (unless --no-cpu-baseline). Without it a run sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the result line, in which both "
+                         "are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the output Csr of the last step (what a caller of the timed "
+                         "path receives) as DIR/<name>.npy; beyond 48 MB a fixed, seeded sample of its rows")
     args = ap.parse_args()
     if args.panel_cols is not None:
         os.environ["BSM_SPMM_PANEL_COLS"] = str(args.panel_cols)
@@ -624,8 +680,12 @@ def main():
             log(f"verify: assembled Y {'==' if verified else '!='} single-GPU Y on {verified_rows:,} rows")
         if launched:
             dist.barrier()
+    if args.dump_outputs and rank == 0:
+        m.sync()
+        files = dump_outputs(args.dump_outputs, m.output(), k)
+        log(f"dump: {files}")
     e2e = None
-    if world == 1 and not args.no_e2e and not f32:
+    if args.full and world == 1 and not args.no_e2e and not f32:
         e2e = end_to_end(args.config, m, x, dev)
         log(f"end to end: {e2e}")
     ms_per_step = elapsed / args.steps * 1e3
@@ -639,7 +699,7 @@ def main():
     achieved_gather = b_gather(my_rows, my_nnz, k, es) / t_k / 1e9
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not f32:
+        if args.full and not args.no_cpu_baseline and world == 1 and not f32:
             log("timing cpu baseline ...")
             cpu = cpu_baseline(args.config, args.cpu_sample_rows)
         traffic, traffic_src, pmc = args.traffic_bytes, "--traffic-bytes" if args.traffic_bytes else None, None

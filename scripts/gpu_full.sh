@@ -17,7 +17,7 @@ run() {
 }
 run gpu_tests 900 python -m pytest tests -m gpu -q -x -p no:cacheprovider --durations=5 || exit $?
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit $?
-run bench 600 python bench.py || exit $?
+run bench 600 python bench.py --full || exit $?
 export TMPDIR=/tmp
 run c5_prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_c5_$TAG -o c5 --output-format csv -- \
     python scripts/solve_c5.py

@@ -31,7 +31,7 @@ for step in "$@"; do
              --timeout 150 --timeout-method thread --durations=8 || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
     bench:*) IFS=: read -r _ cfg extra <<< "$step"
-             run bench_$cfg 600 python bench.py --config $cfg $extra || exit $? ;;
+             run bench_$cfg 600 python bench.py --full --config $cfg $extra || exit $? ;;
     prof:*) IFS=: read -r _ cfg extra <<< "$step"
             run prof_$cfg 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${cfg}_$TAG -o run \
                 --output-format csv -- python bench.py --config $cfg --no-cpu-baseline --no-e2e $extra || exit $? ;;
@@ -44,7 +44,7 @@ for step in "$@"; do
     gather) run gather 300 bash scripts/perf/gather_ceiling.sh || exit $? ;;
     torchrun:*) IFS=: read -r _ cfg extra <<< "$step"
                 run torchrun_$cfg 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-                    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --config $cfg $extra || exit $? ;;
+                    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --full --config $cfg $extra || exit $? ;;
     c5) run c5 600 python scripts/solve_c5.py || exit $? ;;
     py:*) n=$((n + 1)); run py${n} 600 python ${step#py:} || exit $? ;;
     cmd:*) n=$((n + 1)); run cmd${n} 300 ${step#cmd:} || exit $? ;;
