@@ -15,8 +15,8 @@
 //   the extend-add -- U of each child added into its parent's front (the
 //                 lower-level child first, then slot 0: a fixed order, so
 //                 the bits repeat): by default inside the parent's nd_factor
-//                 tiles as they load (the "pull"); BSM_ND_PULL=0 runs
-//                 nd_extend2 (or nd_extend per slot) after each level.
+//                 tiles as they load (the "pull"); the plain pipeline
+//                 (BSM_ND_PLAIN=1) runs nd_extend2 after each level.
 // The solves walk the same levels: forward bottom-up (a child's update
 // vector into its parent), backward top-down (the ancestors' x gathered).
 // Not bit-exact with the reference (another elimination order, FMA); within
@@ -47,7 +47,7 @@ struct NdDev {
     int32_t ld, np, np_pad, m, npt, nt, parent, kid0, kid1;
     int32_t tb_off;     // (child) nt + 1 bounds of the parent's tile rows in ri: tb[t] = first a, ri[a] >= 64 t
     int32_t pull_swap;  // (parent) kid1's update block is added before kid0's (kid1 on a lower level)
-    int32_t tile_off;   // the front's lower tiles' index base (nd_lower_idx) in the plan's per-tile flags
+    int32_t tile_off;   // the front's lower tiles' index base (nd_lower_idx) in the plan's per-tile lists of A
 };
 
 // (I, K), I >= K, among a front's nt (nt + 1) / 2 lower tiles, column by column
@@ -86,40 +86,6 @@ __global__ __launch_bounds__(256) void nd_assemble(int64_t n, const int64_t* __r
         const int64_t lr = r < nd.start + nd.np ? r - nd.start : nd.np_pad + lower_bound_i32(st + nd.st_off, nd.m, r);
         F[nd.foff + lc * nd.ld + lr] = val[e];
     }
-}
-
-// The tiles A's entries land in (once per plan, from the pattern, with
-// nd_assemble's addressing): zf[tile_off + nd_lower_idx] = 1. The others
-// start from zero without being zeroed or read (the pulled extend-add: no
-// kernel writes them before their factor tile).
-__global__ __launch_bounds__(256) void nd_mark_tiles(int64_t n, const int64_t* __restrict__ rp,
-                                                     const int32_t* __restrict__ col, const int32_t* __restrict__ pinv,
-                                                     const int32_t* __restrict__ owner,
-                                                     const NdDev* __restrict__ nodes, const int32_t* __restrict__ st,
-                                                     uint8_t* __restrict__ zf) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t pi = pinv[i];
-    for (int64_t e = rp[i]; e < rp[i + 1]; ++e) {
-        const int64_t j = col[e];
-        if (j > i) continue;
-        const int64_t pj = pinv[j];
-        const int64_t r = pi > pj ? pi : pj, c = pi > pj ? pj : pi;
-        const NdDev& nd = nodes[owner[c]];
-        const int64_t lc = c - nd.start;
-        const int64_t lr = r < nd.start + nd.np ? r - nd.start : nd.np_pad + lower_bound_i32(st + nd.st_off, nd.m, r);
-        zf[nd.tile_off + nd_lower_idx(nd.nt, (int32_t)(lr >> 6), (int32_t)(lc >> 6))] = 1;
-    }
-}
-// the factor's tasks of unmarked tiles: .w |= 2 (a whole-front task keeps its tiles' loads)
-__global__ __launch_bounds__(256) void nd_mark_tasks(int64_t ntasks, const NdDev* __restrict__ nodes,
-                                                     const uint8_t* __restrict__ zf, int4* __restrict__ tiles) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntasks) return;
-    const int4 tl = tiles[t];
-    if (tl.w != 0) return;
-    const NdDev& nd = nodes[tl.x];
-    if (!zf[nd.tile_off + nd_lower_idx(nd.nt, tl.y, tl.z)]) tiles[t].w = 2;
 }
 
 // A's entries by tile (once per plan, from the pattern, with nd_assemble's
@@ -189,24 +155,20 @@ __global__ __launch_bounds__(256) void nd_aent_fill(int64_t n, const int64_t* __
         aent[aoff[g] + slot] = (e << 12) | pos;
     }
 }
-// per factor task (not a whole front): its tile's entry range (offset, count)
+// per factor task: its tile's entry range (offset, count)
 __global__ __launch_bounds__(256) void nd_task_ranges(int64_t ntasks, const int4* __restrict__ tiles,
                                                       const NdDev* __restrict__ nodes, const int32_t* __restrict__ aoff,
                                                       int2* __restrict__ tq) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntasks) return;
     const int4 tl = tiles[t];
-    if (tl.w == 1) {
-        tq[t] = make_int2(0, 0);
-        return;
-    }
     const NdDev& nd = nodes[tl.x];
     const int64_t g = nd.tile_off + nd_lower_idx(nd.nt, tl.y, tl.z);
     tq[t] = make_int2(aoff[g], aoff[g + 1] - aoff[g]);
 }
-// per factor task (not a whole front): its children's blocks, first and
-// second in nd_extend2's order (NdPull::ra = 0: none), so the tile reads
-// them with its task instead of through node -> child -> bounds
+// per factor task: its children's blocks, first and second in nd_extend2's
+// order (NdPull::ra = 0: none), so the tile reads them with its task instead
+// of through node -> child -> bounds (tb)
 struct NdPull {
     int64_t uoff;   // the child's update block U at F + uoff (U[a][b] at uoff + b ld + a)
     int64_t uvoff;  // its update vector at V + uvoff (the folded forward solve)
@@ -222,7 +184,7 @@ __global__ __launch_bounds__(256) void nd_task_pull(int64_t ntasks, const int4* 
     for (int h = 0; h < 2; ++h) {
         NdPull o{0, 0, 0, 0, 0, 0, 0, 0};
         const int c = h == nd.pull_swap ? nd.kid0 : nd.kid1;
-        if (c >= 0 && tl.w != 1) {
+        if (c >= 0) {
             const NdDev& cd = nodes[c];
             const int32_t* const tbc = tb + cd.tb_off;
             o.uoff = cd.foff + (int64_t)cd.np_pad * cd.ld + cd.np_pad;
@@ -249,13 +211,12 @@ __global__ __launch_bounds__(256) void nd_aent_vals(int64_t na, const int64_t* _
 
 // zero the fronts' lower tiles (the only ones any kernel reads: every tile
 // of the factor's lists): 55 % of the bytes a memset of the whole squares
-// writes; with zf, only the tiles A's entries land in (nd_mark_tiles)
+// writes (the plain pipeline; the default one never reads F before writing it)
 template <typename T>
 __global__ __launch_bounds__(256) void nd_zero_tiles(const NdDev* __restrict__ nodes, const int4* __restrict__ tiles,
-                                                     T* __restrict__ F, const uint8_t* __restrict__ zf) {
+                                                     T* __restrict__ F) {
     const int4 tl = tiles[blockIdx.x];
     const NdDev& nd = nodes[tl.x];
-    if (zf && !zf[nd.tile_off + nd_lower_idx(nd.nt, tl.y, tl.z)]) return;
     T* const t0 = F + nd.foff + (int64_t)64 * tl.z * nd.ld + 64 * tl.y;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
@@ -278,13 +239,13 @@ __global__ __launch_bounds__(64) void nd_pad_pivots(const NdDev* __restrict__ no
 //     S = F_IK - sum_{J < min(K, npt)} L_IJ L_KJ^T
 //     K < npt, I == K: L_KK = chol(S), Dinv_K = L_KK^-1   (flag)
 //     K < npt, I >  K: L_IK = S L_KK^-T                    (flag)
-//     K >= npt       : U_IK = S (the update block, for nd_extend)
-// tiles[t] = (node, 0, 0, 1): the whole front of a small node (a few tiles:
-// most of the leaf level) on this workgroup, its tiles in column order one
-// after the other. Its flags are its own (a tile's waits find them set), so
-// it waits on nobody: these tasks follow the tiled fronts' tickets and fill
-// the CUs while those fronts' chains run, without a ticket and a flag
-// hand-off through L2 per tile.
+//     K >= npt       : U_IK = S (the update block, for the extend-add)
+// aent (the default pipeline): the tile starts from A's entries in it, staged
+// from the plan's per-tile lists, plus its children's update blocks pulled
+// through the task's descriptors (pdesc), and a diagonal tile skips its
+// padding panels. aent == nullptr (the plain pipeline): the tile is read
+// from F as nd_zero_tiles, nd_assemble, nd_pad_pivots and nd_extend2 left it,
+// nothing is pulled or folded, and all four diagonal panels are factored.
 // fV (the forward solve folded in, one right-hand side; BSM_ND_FOLD): the
 // diagonal tile (I, I) also forms w_I = b_I + the children's update-vector
 // entries landing in its rows - sum_{J < min(I, npt)} L_IJ y_J (the L_IJ are
@@ -303,12 +264,10 @@ template <typename T, bool STAMPS = false>
 __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ nodes, const int4* __restrict__ tiles,
                                                  int64_t ntiles, T* __restrict__ F, T* __restrict__ Dinv,
                                                  int* __restrict__ flags, int* __restrict__ ticket,
-                                                 int* __restrict__ status, int pad_skip,
-                                                 const int32_t* __restrict__ tb, const int32_t* __restrict__ ri,
-                                                 int zskip, T* __restrict__ fV, const T* __restrict__ fbp,
+                                                 int* __restrict__ status, const int32_t* __restrict__ ri,
+                                                 T* __restrict__ fV, const T* __restrict__ fbp,
                                                  const int64_t* __restrict__ aent, const T* __restrict__ av,
-                                                 const int32_t* __restrict__ aoff, const int2* __restrict__ tq,
-                                                 const NdPull* __restrict__ pdesc,
+                                                 const int2* __restrict__ tq, const NdPull* __restrict__ pdesc,
                                                  unsigned long long* __restrict__ stamps = nullptr) {
     long long c_wait = 0, c_prod = 0, c_diag = 0, c_trsm = 0, c_upd = 0, c_drain = 0;
     long long n_prod = 0, n_diag = 0, n_trsm = 0, n_upd = 0, c_total = 0, n_tiles = 0;
@@ -342,16 +301,10 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
     __syncthreads();
     int64_t t = __builtin_amdgcn_readfirstlane(tk);
     while (t < ntiles) {
-      const int4 tl = tiles[t];
-      const NdDev& nd = nodes[tl.x];
-      const bool whole = tl.w == 1;
-      // zskip: a tile no A entry lands in starts from zero (tl.w == 2,
-      // nd_mark_tasks): it was neither zeroed nor written, and is not read
-      const bool fz = zskip && tl.w == 2;
-      const int npt = nd.npt, ntf = nd.nt;
-      const int cnt = whole ? ntf * (ntf + 1) / 2 : 1;
-      int I = whole ? 0 : tl.y, K = whole ? 0 : tl.z;
-      for (int jt = 0; jt < cnt; ++jt) {
+        const int4 tl = tiles[t];
+        const NdDev& nd = nodes[tl.x];
+        const int npt = nd.npt;
+        const int I = tl.y, K = tl.z;
         const int64_t ld = nd.ld;
         T* const Fn = F + nd.foff;
         int* const fl = flags + nd.flag_off;
@@ -376,16 +329,16 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
         // the folded forward solve on this diagonal tile: w = b (pivot rows)
         const bool fold = fV && I == K;
         if (fold && tid < 64) fw[tid] = 64 * K + tid < nd.np ? fbp[nd.start + 64 * K + tid] : (T)0;
-        const bool kids = tb && (nd.kid0 >= 0 || nd.kid1 >= 0);
-        if (kids || aent) {
-            // aent: the tile starts from A's entries in it (and the padding
+        if (aent) {
+            // The tile starts from A's entries in it (and the padding
             // pivots' identity), staged in LDS from the plan's per-tile lists,
             // instead of from F (no zeroing, no assembly, no read of F): the
             // same values, written the same way.
-            // The children's update blocks, pulled into this tile (tb: no
-            // nd_extend launches): the entries (a, b), a >= b, of child c
+            // The children's update blocks, pulled into this tile (no
+            // nd_extend2 launches): the entries (a, b), a >= b, of child c
             // with ri[a] in tile row I and ri[b] in tile column K, i.e. a in
-            // [tb[I], tb[I + 1]), b in [tb[K], tb[K + 1]) (ri ascending).
+            // [tb[I], tb[I + 1]), b in [tb[K], tb[K + 1]) (ri ascending; the
+            // task's descriptors hold these ranges, nd_task_pull).
             // The tile goes to LDS by coalesced columns; thread (lane, wave)
             // takes the child's a = a0 + lane and b = b0 + 4 u + w, its
             // row's place one load per lane and the columns' places through
@@ -403,34 +356,16 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
                 int ld, a0, ra, b0, rbn;
             } bk[2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                bk[h].ra = 0;
-                if (!kids) continue;
-                if (pdesc && !whole) {  // the task's own descriptors (nd_task_pull)
-                    const NdPull& o = pdesc[2 * t + h];
-                    bk[h].U = F + o.uoff;
-                    bk[h].rc = ri + o.rcoff;
-                    bk[h].u = fV ? fV + o.uvoff : nullptr;
-                    bk[h].ld = o.ld;
-                    bk[h].a0 = o.a0;
-                    bk[h].ra = o.ra;
-                    bk[h].b0 = o.b0;
-                    bk[h].rbn = o.rbn;
-                    continue;
-                }
-                const int c = h == nd.pull_swap ? nd.kid0 : nd.kid1;
-                if (c < 0) continue;
-                const NdDev& cd = nodes[c];
-                const int32_t* const tbc = tb + cd.tb_off;
-                bk[h].U = F + cd.foff + (int64_t)cd.np_pad * cd.ld + cd.np_pad;  // U[a][b] at U[b ld + a]
-                bk[h].rc = ri + cd.st_off;
-                bk[h].u = fV ? fV + cd.voff + cd.np_pad : nullptr;
-                bk[h].ld = cd.ld;
-                bk[h].a0 = tbc[I];
-                bk[h].ra = tbc[I + 1] - bk[h].a0;
-                bk[h].b0 = tbc[K];
-                bk[h].rbn = tbc[K + 1] - bk[h].b0;
-                if (bk[h].rbn <= 0) bk[h].ra = 0;
+            for (int h = 0; h < 2; ++h) {  // ra = 0: no such child, or none of its entries in this tile
+                const NdPull& o = pdesc[2 * t + h];
+                bk[h].U = F + o.uoff;
+                bk[h].rc = ri + o.rcoff;
+                bk[h].u = fV ? fV + o.uvoff : nullptr;
+                bk[h].ld = o.ld;
+                bk[h].a0 = o.a0;
+                bk[h].ra = o.ra;
+                bk[h].b0 = o.b0;
+                bk[h].rbn = o.rbn;
             }
             T v[16];
             int pr[2] = {0, 0};
@@ -460,32 +395,15 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
                 }
                 if (fold && w == 0 && lane < k.ra) fw[pr[h]] += uv;
             };
-            if (aent) {
-                int2 rq;
-                if (whole) {
-                    const int64_t g = nd.tile_off + nd_lower_idx(ntf, I, K);
-                    rq = make_int2(aoff[g], aoff[g + 1] - aoff[g]);
-                } else {
-                    rq = tq[t];
-                }
+            const int2 rq = tq[t];
 #pragma unroll
-                for (int u = 0; u < 16; ++u) PT[lane][4 * u + w] = (T)0;
-                __syncthreads();
-                for (int q = tid; q < rq.y; q += 256) {
-                    const int64_t x = aent[rq.x + q];
-                    PT[x & 63][(x >> 6) & 63] = av[rq.x + q];
-                }
-                if (I == K && K < npt && tid < 64 && 64 * K + tid >= nd.np) PT[tid][tid] = (T)1;
-            } else {
-                T fv[16];  // the tile by columns: element (lane, 4 u + w)
-#pragma unroll
-                for (int u = 0; u < 16; ++u) fv[u] = (T)0;
-                if (!fz)
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) fv[u] = Fn[(int64_t)(64 * K + 4 * u + w) * ld + 64 * I + lane];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) PT[lane][4 * u + w] = fv[u];
+            for (int u = 0; u < 16; ++u) PT[lane][4 * u + w] = (T)0;
+            __syncthreads();
+            for (int q = tid; q < rq.y; q += 256) {
+                const int64_t x = aent[rq.x + q];
+                PT[x & 63][(x >> 6) & 63] = av[rq.x + q];
             }
+            if (I == K && K < npt && tid < 64 && 64 * K + tid >= nd.np) PT[tid][tid] = (T)1;
             if (bk[0].ra > 0) issue(bk[0]);
             long long ps = 0;
             auto pstamp = [&](int i) {
@@ -513,11 +431,6 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
                 for (int q = 0; q < 4; ++q) acc[cb][q] = PT[rb + 4 * q][16 * cb + cm];
             __syncthreads();  // PT is the products' staging next
             pstamp(3);
-        } else if (fz) {
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[cb][q] = (T)0;
         } else {
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
@@ -526,8 +439,9 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
                     acc[cb][q] = Fn[(int64_t)(64 * K + 16 * cb + cm) * ld + 64 * I + rb + 4 * q];
         }
         // left-looking products (two workgroups per CU: __launch_bounds__
-        // (256, 2) keeps the VGPRs at 128; at 136 the occupancy query gave one
-        // and the C5 factor took 8.5 instead of 5.7 ms)
+        // (256, 2) caps the registers at 256 per lane; the f64 kernel uses
+        // 255 with no scratch. With one workgroup per CU the C5 factor took
+        // 8.5 instead of 5.7 ms)
         const int Jn = K < npt ? K : npt;
         T fp = (T)0;  // fold: this thread's share of (L_IJ y_J)[lane], terms 16 w .. 16 w + 15
         for (int J = 0; J < Jn; ++J) {
@@ -570,10 +484,11 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
                 for (int q = 0; q < 4; ++q) PT[rb + 4 * q][16 * cb + cm] = acc[cb][q];
             __syncthreads();
             // the panels holding real pivots (the front's last pivot tile may
-            // end in identity padding: blk_diag_panels skips those panels)
+            // end in identity padding: blk_diag_panels skips those panels;
+            // the plain pipeline factors all four)
             const int rem = nd.np - 64 * K;
             blk_diag_panels<T>(PTl, QTl, (lds_t<T>*)Di, (lds_t<T>*)Tb, (lds_t<T>*)rd, status, tid, nullptr, nullptr,
-                               nullptr, nullptr, rem >= 64 || !pad_skip ? 4 : (rem + 15) / 16);
+                               nullptr, nullptr, rem >= 64 || !aent ? 4 : (rem + 15) / 16);
             __syncthreads();
             T* const dk = Dinv + nd.dinv_off + (int64_t)K * 4096;
 #pragma unroll
@@ -633,15 +548,10 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
         __syncthreads();
         if (K < npt && tid == 0) __hip_atomic_store(&fl[I * npt + K], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (STAMPS) c_drain += (long long)clock64() - c2, ++n_tiles;
-        if (++I == ntf) {  // a whole front: the next tile in column order
-            ++K;
-            I = K;
-        }
-      }
-      __syncthreads();
-      if (tid == 0) tk = atomicAdd(ticket, 1);
-      __syncthreads();
-      t = __builtin_amdgcn_readfirstlane(tk);
+        __syncthreads();
+        if (tid == 0) tk = atomicAdd(ticket, 1);
+        __syncthreads();
+        t = __builtin_amdgcn_readfirstlane(tk);
     }
     if (STAMPS && tid == 0) {
         c_total = (long long)clock64() - c_start;
@@ -652,31 +562,14 @@ __global__ __launch_bounds__(256, 2) void nd_factor(const NdDev* __restrict__ no
     }
 }
 
-// U of a child into its parent's front: task (child, b) adds column b of the
-// child's update block, rows a >= b, at (ri[a], ri[b]). One wave per task.
-template <typename T>
-__global__ __launch_bounds__(256) void nd_extend(const NdDev* __restrict__ nodes, const int2* __restrict__ tasks,
-                                                 int64_t ntasks, const int32_t* __restrict__ ri, T* __restrict__ F) {
-    const int64_t task = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (task >= ntasks) return;
-    const int lane = threadIdx.x & 63;
-    const int2 tk = tasks[task];
-    const NdDev& c = nodes[tk.x];
-    const NdDev& p = nodes[c.parent];
-    const int32_t* rc = ri + c.st_off;
-    const int b = tk.y;
-    const T* src = F + c.foff + (int64_t)(c.np_pad + b) * c.ld + c.np_pad;
-    T* dst = F + p.foff + (int64_t)rc[b] * p.ld;
-    for (int a = b + lane; a < c.m; a += 64) dst[rc[a]] += src[a];
-}
-
-// Both children of a parent in one launch: task (c0, b0, c1, b1) adds column
-// b0 of child c0's update block, then column b1 of child c1's, into the SAME
-// parent column (ri[b0] of c0 == ri[b1] of c1; -1: that child has none), in
-// that order, on one wave: the same sums in the same order as a slot-0 launch
-// followed by a slot-1 launch, and the tasks of a launch own distinct parent
-// columns. The second child's loads are write-through (the first child's
-// stores came from other lanes of this wave) after the wave's stores drain.
+// U of the children into their parent's front (the plain pipeline), both
+// children of a parent in one launch: task (c0, b0, c1, b1) adds column b0 of
+// child c0's update block, rows a >= b0, at (ri[a], ri[b0]), then column b1
+// of child c1's, into the SAME parent column (ri[b0] of c0 == ri[b1] of c1;
+// -1: that child has none), in that order, on one wave; the tasks of a
+// launch own distinct parent columns. The second child's loads are
+// write-through (the first child's stores came from other lanes of this
+// wave) after the wave's stores drain.
 template <typename T>
 __global__ __launch_bounds__(256) void nd_extend2(const NdDev* __restrict__ nodes, const int4* __restrict__ tasks,
                                                   int64_t ntasks, const int32_t* __restrict__ ri, T* __restrict__ F) {
@@ -1167,31 +1060,26 @@ inline unsigned nd_blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b)
 struct NdLayout {
     std::vector<NdDev> dev;
     std::vector<int32_t> st, ri, pinv, owner, lvl_nodes;
-    std::vector<int32_t> tb;   // per child: its rows' bounds per tile row of the parent (NdDev::tb_off)
-    std::vector<int4> tiles;   // nd_factor's tasks: tiles of the tiled fronts, then the small fronts whole
-    std::vector<int4> ztiles;  // every front's lower tiles (nd_zero_tiles)
-    std::vector<int2> ext;
-    std::vector<int64_t> tiles_off, lvl_off, ext_off;  // per level (ext: per level and slot)
-    std::vector<int4> ext2;                             // nd_extend2's tasks (both slots)
-    std::vector<int64_t> ext2_off;                      // per level
-    std::vector<int2> ftasks;                           // nd_forward_tiles' (node, tile row), I-major
-    std::vector<int64_t> ftask_off;                     // per level
-    std::vector<int2> btasks;                           // nd_backward_tiles' (node, pivot tile), last tiles first
-    std::vector<int64_t> btask_off;                     // per level
+    std::vector<int32_t> tb;  // per child: its rows' bounds per tile row of the parent (NdDev::tb_off)
+    std::vector<int4> tiles;  // nd_factor's tasks: every front's lower tiles (nd_zero_tiles' too)
+    std::vector<int64_t> tiles_off, lvl_off;  // per level
+    std::vector<int4> ext2;                    // nd_extend2's tasks (the plain pipeline)
+    std::vector<int64_t> ext2_off;             // per level
+    std::vector<int2> ftasks;                  // nd_forward_tiles' (node, tile row), I-major
+    std::vector<int64_t> ftask_off;            // per level
+    std::vector<int2> btasks;                  // nd_backward_tiles' (node, pivot tile), last tiles first
+    std::vector<int64_t> btask_off;            // per level
     int64_t f_elems = 0, dinv_elems = 0, n_flags = 0, vtot = 0, n_lower = 0;
 };
 
-// lay: the layout's options. Bits 0-15: fronts of at most this many tile
-// rows are one whole-front task of nd_factor (0: every front by tiles); bit
-// 16: the per-slot extend lists too (BSM_ND_EXT_MERGE=0's A/B path; ~1M
-// entries at C5 that the default merged launches never read); bits 17-27:
-// the lag of the tiles below a diagonal, in fronts (0: none); bit 28: the
-// extend-add by nd_extend2 / nd_extend launches (BSM_ND_PULL=0) instead of
-// inside nd_factor's tile loads (the extend task lists are only built then)
-void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
-    const int32_t small_nt = lay & 0xffff;
-    const bool per_slot = (lay >> 16) & 1;
-    const bool push = (lay >> 28) & 1;
+// The layout's options: part of the plan's keys
+struct NdLay {
+    int32_t lag = 0;     // the tiles below a diagonal follow it by this many fronts' diagonals (0: by all of them)
+    bool plain = false;  // the extend-add by nd_extend2 launches (their task lists are built only then)
+    bool operator==(const NdLay& o) const { return lag == o.lag && plain == o.plain; }
+};
+
+void nd_layout(const NdPlan& P, NdLay lay, NdLayout& L) {
     const int32_t nn = (int32_t)P.nodes.size();
     L.dev.resize((size_t)nn);
     int64_t st_total = 0;
@@ -1284,21 +1172,19 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
             zt += (size_t)d.nt * (d.nt + 1) / 2;
             ft += (size_t)d.nt;
             bt += (size_t)d.npt;
-            ex += d.parent >= 0 && push ? (size_t)d.m : 0;
+            ex += d.parent >= 0 && lay.plain ? (size_t)d.m : 0;
         }
-        L.ztiles.reserve(zt);
         L.tiles.reserve(zt);
         L.ftasks.reserve(ft);
         L.btasks.reserve(bt);
-        if (per_slot) L.ext.reserve(ex);
         L.ext2.reserve(ex);
         L.lvl_nodes.reserve((size_t)nn);
     }
     // The levels' lists are independent: built on threads (the leaf level,
     // the largest, sets the time), then concatenated in level order
     struct LevelLists {
-        std::vector<int4> zt, tiles, ext2;
-        std::vector<int2> ext[2], ft, bt;
+        std::vector<int4> tiles, ext2;
+        std::vector<int2> ft, bt;
     };
     std::vector<LevelLists> per((size_t)P.n_levels);
     auto build_level = [&](size_t li) {
@@ -1307,29 +1193,22 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
         std::vector<char> used;  // the merge walk's marks, reused
         int32_t kmax = 0;
         for (int32_t i : lv) kmax = std::max(kmax, L.dev[(size_t)i].nt);
-        // every front's lower tiles (nd_zero_tiles)
-        for (int32_t i : lv)
-            for (int32_t K = 0; K < L.dev[(size_t)i].nt; ++K)
-                for (int32_t I = K; I < L.dev[(size_t)i].nt; ++I) o.zt.push_back(make_int4(i, I, K, 0));
-        // tiled fronts, column K of every front: the diagonal tiles first,
-        // then the tiles below (which wait for their diagonal tile's
-        // inverse), so the waiting tiles' diagonals are well under way when
-        // they are taken; then the small fronts, one task each
-        // With a lag (bits 17-27 of lay, in fronts), a front's tiles below the
+        // column K of every front: the diagonal tiles first, then the tiles
+        // below (which wait for their diagonal tile's inverse), so the
+        // waiting tiles' diagonals are well under way when they are taken.
+        // With a lag (lay.lag, in fronts), a front's tiles below the
         // diagonal follow its diagonal tile by `lag` fronts' diagonals
         // instead of all of them: at about the grid's size (512 workgroups)
         // the diagonal is done when they are taken, and the level's other
         // fronts are not held up behind the whole column of diagonals. 0: all
         // of a column's diagonal tiles first (round 5). Either way a tile only
         // waits on earlier tickets.
-        auto small = [&](int32_t i) { return L.dev[(size_t)i].nt <= small_nt; };
-        const size_t lag_units = (size_t)((lay >> 17) & 0x7ff);
         std::vector<int32_t> fr;
         for (int32_t K = 0; K < kmax; ++K) {
             fr.clear();
             for (int32_t i : lv)
-                if (!small(i) && K < L.dev[(size_t)i].nt) fr.push_back(i);
-            const size_t nf = fr.size(), lag = lag_units ? lag_units : nf;
+                if (K < L.dev[(size_t)i].nt) fr.push_back(i);
+            const size_t nf = fr.size(), lag = lay.lag ? (size_t)lay.lag : nf;
             for (size_t idx = 0; idx < nf + lag; ++idx) {
                 if (idx < nf) o.tiles.push_back(make_int4(fr[idx], K, K, 0));
                 if (idx >= lag && idx - lag < nf) {
@@ -1338,14 +1217,6 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
                 }
             }
         }
-        for (int32_t i : lv)
-            if (small(i)) o.tiles.push_back(make_int4(i, 0, 0, 1));
-        for (int s = 0; s < 2 && per_slot && push; ++s)
-            for (int32_t i : lv) {
-                const NdNode& x = P.nodes[(size_t)i];
-                if (x.parent < 0 || x.slot != s) continue;
-                for (int32_t b = 0; b < L.dev[(size_t)i].m; ++b) o.ext[s].push_back(make_int2(i, b));
-            }
         for (int32_t I = 0; I < kmax; ++I)
             for (int32_t i : lv)
                 if (I < L.dev[(size_t)i].nt) o.ft.push_back(make_int2(i, I));
@@ -1354,7 +1225,7 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
         for (int32_t d = 0; d < pmax; ++d)
             for (int32_t i : lv)
                 if (d < L.dev[(size_t)i].npt) o.bt.push_back(make_int2(i, L.dev[(size_t)i].npt - 1 - d));
-        if (lv.empty() || !push) return;
+        if (lv.empty() || !lay.plain) return;
         // both slots in one launch: a slot-0 child's columns, each paired with
         // the slot-1 sibling's column landing on the same parent column when
         // that sibling is on this level too, then the sibling's unpaired ones
@@ -1403,12 +1274,7 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
         L.lvl_off.push_back((int64_t)L.lvl_nodes.size());
         L.lvl_nodes.insert(L.lvl_nodes.end(), lv.begin(), lv.end());
         L.tiles_off.push_back((int64_t)L.tiles.size());
-        L.ztiles.insert(L.ztiles.end(), o.zt.begin(), o.zt.end());
         L.tiles.insert(L.tiles.end(), o.tiles.begin(), o.tiles.end());
-        for (int sl = 0; sl < 2; ++sl) {
-            L.ext_off.push_back((int64_t)L.ext.size());
-            L.ext.insert(L.ext.end(), o.ext[sl].begin(), o.ext[sl].end());
-        }
         L.ftask_off.push_back((int64_t)L.ftasks.size());
         L.ftasks.insert(L.ftasks.end(), o.ft.begin(), o.ft.end());
         L.btask_off.push_back((int64_t)L.btasks.size());
@@ -1418,7 +1284,6 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
     }
     L.lvl_off.push_back((int64_t)L.lvl_nodes.size());
     L.tiles_off.push_back((int64_t)L.tiles.size());
-    L.ext_off.push_back((int64_t)L.ext.size());
     L.ext2_off.push_back((int64_t)L.ext2.size());
     L.ftask_off.push_back((int64_t)L.ftasks.size());
     L.btask_off.push_back((int64_t)L.btasks.size());
@@ -1432,15 +1297,15 @@ void nd_layout(const NdPlan& P, int32_t lay, NdLayout& L) {
 struct NdCached {
     int64_t leaf = 0;
     int32_t nn = 0, n_levels = 0;
-    std::vector<int64_t> tiles_off, lvl_off, ext_off, ext2_off, ftask_off, btask_off;
+    std::vector<int64_t> tiles_off, lvl_off, ext2_off, ftask_off, btask_off;
     int64_t f_elems = 0, dinv_elems = 0, n_flags = 0, vtot = 0, max_front = 0;
-    size_t o_dev = 0, o_st = 0, o_ri = 0, o_pinv = 0, o_owner = 0, o_lvl = 0, o_tiles = 0, o_ext = 0, o_ext2 = 0,
-           o_ftask = 0, o_btask = 0, o_perm = 0, o_ztiles = 0, o_tb = 0, o_zf = 0;
-    size_t n_tiles = 0, n_ztiles = 0, n_ext = 0;
+    size_t o_dev = 0, o_st = 0, o_ri = 0, o_pinv = 0, o_owner = 0, o_lvl = 0, o_tiles = 0, o_ext2 = 0, o_ftask = 0,
+           o_btask = 0, o_perm = 0, o_tb = 0;
+    size_t n_tiles = 0, n_ext2 = 0;
     int64_t n_lower = 0, n_aent = 0;  // the fronts' lower tiles; A's lower entries
-    DBuf aoff, aent, tq;              // A's entries by tile (nd_aent_*), per task ranges
-    DBuf pdesc;                       // per task: its children's blocks (nd_task_pull)
-    int32_t small_nt = 0;
+    DBuf aent, tq;                    // the default pipeline: A's entries by tile (nd_aent_*), per task ranges
+    DBuf pdesc;                       // and per task its children's blocks (nd_task_pull)
+    NdLay lay;
     double ms_graph = 0, ms_order = 0, ms_symbolic = 0, ms_layout = 0, ms_pack = 0;
     DBuf plan;
     // The numeric storage (fronts, inverse diagonal tiles, flags) stays with
@@ -1452,17 +1317,10 @@ struct NdCached {
     std::mutex num_mu;
     DBuf fr, dv, fl;
     std::atomic<size_t> kept_bytes{0};  // fr + dv + fl, written under num_mu
-    hipEvent_t fr_zeroed = nullptr;     // fr was just allocated and is being zeroed (nd_build_plan)
     // drop the kept numeric storage unless a solve holds it
-    void drop_zeroed() {  // fr no longer the freshly zeroed allocation (under num_mu)
-        if (fr_zeroed) (void)hipEventDestroy(fr_zeroed);
-        fr_zeroed = nullptr;
-    }
-    ~NdCached() { drop_zeroed(); }
     bool release_numeric() {
         std::unique_lock<std::mutex> l(num_mu, std::try_to_lock);
         if (!l.owns_lock()) return false;
-        drop_zeroed();
         fr.reset();
         dv.reset();
         fl.reset();
@@ -1533,11 +1391,11 @@ __global__ __launch_bounds__(256) void nd_pattern_diff(const int64_t* __restrict
 
 struct NdKey {
     int device = 0;
-    int32_t small_nt = 0;
+    NdLay lay;
     int64_t n = 0, leaf = 0;
     uint64_t nnz = 0, h0 = 0, h1 = 0;
     bool operator==(const NdKey& o) const {
-        return device == o.device && small_nt == o.small_nt && n == o.n && leaf == o.leaf && nnz == o.nnz &&
+        return device == o.device && lay == o.lay && n == o.n && leaf == o.leaf && nnz == o.nnz &&
                h0 == o.h0 && h1 == o.h1;
     }
 };
@@ -1560,9 +1418,40 @@ NdCache& nd_cache() {  // never destroyed: no hipFree after the runtime's teardo
     return *c;
 }
 
-size_t nd_cache_limit(const char* env, size_t dflt) {
-    const char* e = getenv(env);
-    return e ? (size_t)atoll(e) : dflt;
+// The environment's switches (README.md), read once per solve
+struct NdOpts {
+    int64_t leaf;  // C5 leaf sweep: 128 / 192 / 256 / 320 -> 11.9 / 11.4 / 12.3 / 12.5 ms
+    NdLay lay;     // BSM_ND_LAG, BSM_ND_PLAIN
+    int threads;   // the host analysis' workers
+    bool cache, shared, keep;  // the plan on the handle; across handles; its numeric storage kept too
+    size_t cache_entries, cache_mb;
+    bool fold;                 // one right-hand side: the forward solve inside the factor
+    int fwd_tiles, bwd_tiles;  // the solves by tiles: 0 never, 1 every level, 2 levels with fewer pairs than CUs
+    bool poison, hash_zero, trace, stamps;  // tests and diagnostics
+};
+NdOpts nd_options() {
+    auto num = [](const char* name, long long dflt) {
+        const char* e = getenv(name);
+        return e ? atoll(e) : dflt;
+    };
+    NdOpts o;
+    o.leaf = num("BSM_ND_LEAF", 192);
+    o.lay.lag = (int32_t)std::min(0x7ffll, std::max(0ll, num("BSM_ND_LAG", 512)));
+    o.lay.plain = num("BSM_ND_PLAIN", 0) == 1;
+    o.threads = (int)num("BSM_ND_THREADS", std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())));
+    o.cache = num("BSM_ND_CACHE", 1) != 0;
+    o.shared = o.cache && num("BSM_ND_SHARED", 1) != 0;
+    o.keep = o.cache && num("BSM_ND_KEEP", 1) != 0;
+    o.cache_entries = (size_t)num("BSM_ND_CACHE_ENTRIES", 4);
+    o.cache_mb = (size_t)num("BSM_ND_CACHE_MB", 32768);
+    o.fold = num("BSM_ND_FOLD", 1) != 0;
+    o.fwd_tiles = (int)num("BSM_ND_FWD_TILES", 2);
+    o.bwd_tiles = (int)num("BSM_ND_BWD_TILES", 2);
+    o.poison = num("BSM_ND_POISON", 0) == 1;
+    o.hash_zero = num("BSM_ND_HASH_ZERO", 0) == 1;
+    o.trace = getenv("BSM_ND_TRACE") != nullptr;
+    o.stamps = num("BSM_ND_STAMPS", 0) == 1;
+    return o;
 }
 
 // The calling thread's page-locked staging buffer (grown on demand, kept for
@@ -1595,7 +1484,7 @@ int pinned_staging(size_t bytes, char** out) {
 // An upper bound of nd_build_plan's packed plan bytes, from the analysis
 // alone (the same arrays as the layout; the merged extend tasks and the
 // factor's tasks are at most the child columns and the lower tiles)
-size_t nd_plan_bytes_bound(const NdPlan& P, int32_t lay) {
+size_t nd_plan_bytes_bound(const NdPlan& P, NdLay lay) {
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     size_t sm = 0, zt = 0, ft = 0, bt = 0;
     for (const auto& x : P.nodes) {
@@ -1606,18 +1495,16 @@ size_t nd_plan_bytes_bound(const NdPlan& P, int32_t lay) {
         bt += (size_t)npt;
     }
     const size_t nn = P.nodes.size(), n = (size_t)P.n;
-    const bool push = (lay >> 28) & 1;
     // the children's tile bounds: at most two children of nt + 1 per node
     return al(nn * sizeof(NdDev)) + 2 * al(sm * 4) + 2 * al(n * 4) + al(nn * 4) + al(zt * sizeof(int4)) +
-           al(push && ((lay >> 16) & 1) ? sm * sizeof(int2) : 0) + al(push ? sm * sizeof(int4) : 0) +
-           al(ft * sizeof(int2)) + al(bt * sizeof(int2)) + al(n * 8) + al(zt * sizeof(int4)) +
-           al(2 * (ft + nn) * 4) + al(zt);
+           al(lay.plain ? sm * sizeof(int4) : 0) + al(ft * sizeof(int2)) + al(bt * sizeof(int2)) + al(n * 8) +
+           al(2 * (ft + nn) * 4);
 }
 
 // es > 0: the fronts (es-byte values) are allocated into C.fr on a helper
 // thread while the layout, the packing and the plan's upload run: a first
 // solve's 5 GB hipMalloc (C5) then costs no time of its own
-int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, hipStream_t s, NdCached& C) {
+int nd_build_plan(const bsm_csr* a, int64_t leaf, NdLay lay, int threads, size_t es, hipStream_t s, NdCached& C) {
     const int64_t N = (int64_t)a->rows;
     // A's pattern to the host for the analysis
     char* stg = nullptr;
@@ -1630,8 +1517,6 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
         BSM_HIP_TRY(hipMemcpyAsync(stg + rp_bytes, a->col, (size_t)a->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     BSM_HIP_TRY(hipStreamSynchronize(s));
     stage_mark("nd_pattern_d2h", s);
-    const char* te = getenv("BSM_ND_THREADS");
-    const int threads = te ? atoi(te) : (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
     NdPlan P;
     const int arc = nd_analyse(N, rp, cl, leaf, threads, P);
     BSM_REQUIRE(arc == 0, BSM_ERR_UNSUPPORTED,
@@ -1647,7 +1532,7 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
     // read): the plan's device buffer and the calling thread's page-locked
     // staging buffer, both at an upper bound of the packed plan (~42 MB at
     // C5), so the packing and the upload below allocate nothing
-    const size_t plan_bound = nd_plan_bytes_bound(P, small_nt);
+    const size_t plan_bound = nd_plan_bytes_bound(P, lay);
     PinnedStage* const stage = &pinned_stage();
     {
         const int dev0 = a->device;
@@ -1679,42 +1564,22 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
         const size_t dv_bytes = (size_t)std::max<int64_t>(dinv_elems, 1) * es;
         const size_t fl_bytes = ((size_t)n_flags + (size_t)P.n_levels + 2) * sizeof(int);
         const int dev = a->device;
-        // BSM_ND_PREZERO=1: also zeroed whole there, on a stream of its own
-        // (round 6 before the marked tiles: a fresh allocation's first touch
-        // cost ~10 ms at C5 inside the solve's first kernel). Off by default:
-        // with the layout at ~6 ms the solve waited ~7 ms for that memset,
-        // while zeroing only the marked tiles in the solve takes ~3 ms
-        // (profiles/r06_m_*)
-        const char* pze = getenv("BSM_ND_PREZERO");
-        const bool prezero = pze && atoi(pze) == 1;
-        pre_fronts = std::thread([&C, f_elems, es, dev, prezero, dv_bytes, fl_bytes] {
+        pre_fronts = std::thread([&C, f_elems, es, dev, dv_bytes, fl_bytes] {
             if (hipSetDevice(dev) != hipSuccess || C.fr.alloc((size_t)f_elems * es) != BSM_OK) return;
             (void)C.dv.alloc(dv_bytes);  // nd_solve allocates again if this failed
             (void)C.fl.alloc(fl_bytes);
-            if (!prezero) return;
-            hipStream_t z = nullptr;
-            hipEvent_t ev = nullptr;
-            if (hipStreamCreateWithFlags(&z, hipStreamNonBlocking) != hipSuccess) return;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess &&
-                hipMemsetAsync(C.fr.p, 0, C.fr.bytes, z) == hipSuccess && hipEventRecord(ev, z) == hipSuccess) {
-                C.fr_zeroed = ev;  // nd_solve waits for it and skips nd_zero_tiles once
-            } else if (ev) {
-                (void)hipEventDestroy(ev);
-            }
-            (void)hipStreamDestroy(z);  // released once its work is done
         });
     }
     const auto tl0 = host_now();
     NdLayout L;
-    C.small_nt = small_nt;
-    nd_layout(P, small_nt, L);
+    C.lay = lay;
+    nd_layout(P, lay, L);
     C.ms_layout = ms_since(tl0);
     C.leaf = leaf;
     C.nn = (int32_t)L.dev.size();
     C.n_levels = P.n_levels;
     C.tiles_off = L.tiles_off;
     C.lvl_off = L.lvl_off;
-    C.ext_off = L.ext_off;
     C.ext2_off = L.ext2_off;
     C.ftask_off = L.ftask_off;
     C.btask_off = L.btask_off;
@@ -1724,8 +1589,7 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
     C.vtot = L.vtot;
     C.n_tiles = L.tiles.size();
     C.n_lower = L.n_lower;
-    C.n_ztiles = L.ztiles.size();
-    C.n_ext = L.ext.size();
+    C.n_ext2 = L.ext2.size();
     C.ms_graph = P.ms_graph;
     C.ms_order = P.ms_order;
     C.ms_symbolic = P.ms_symbolic;
@@ -1739,15 +1603,12 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
     C.o_owner = C.o_pinv + al(L.pinv.size() * 4);
     C.o_lvl = C.o_owner + al(L.owner.size() * 4);
     C.o_tiles = C.o_lvl + al(L.lvl_nodes.size() * 4);
-    C.o_ext = C.o_tiles + al(L.tiles.size() * sizeof(int4));
-    C.o_ext2 = C.o_ext + al(L.ext.size() * sizeof(int2));
+    C.o_ext2 = C.o_tiles + al(L.tiles.size() * sizeof(int4));
     C.o_ftask = C.o_ext2 + al(L.ext2.size() * sizeof(int4));
     C.o_btask = C.o_ftask + al(L.ftasks.size() * sizeof(int2));
     C.o_perm = C.o_btask + al(L.btasks.size() * sizeof(int2));
-    C.o_ztiles = C.o_perm + al((size_t)N * 8);
-    C.o_tb = C.o_ztiles + al(L.ztiles.size() * sizeof(int4));
-    C.o_zf = C.o_tb + al(L.tb.size() * 4);
-    const size_t total = C.o_zf + al((size_t)L.n_lower);
+    C.o_tb = C.o_perm + al((size_t)N * 8);
+    const size_t total = C.o_tb + al(L.tb.size() * 4);
     if (pre.joinable()) pre.join();  // the plan's buffers (device, page-locked staging)
     const auto tp0 = host_now();
     char* hp = nullptr;
@@ -1771,12 +1632,10 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
     put(C.o_owner, L.owner.data(), L.owner.size() * 4);
     put(C.o_lvl, L.lvl_nodes.data(), L.lvl_nodes.size() * 4);
     put(C.o_tiles, L.tiles.data(), L.tiles.size() * sizeof(int4));
-    put(C.o_ext, L.ext.data(), L.ext.size() * sizeof(int2));
     put(C.o_ext2, L.ext2.data(), L.ext2.size() * sizeof(int4));
     put(C.o_ftask, L.ftasks.data(), L.ftasks.size() * sizeof(int2));
     put(C.o_btask, L.btasks.data(), L.btasks.size() * sizeof(int2));
     put(C.o_perm, P.perm.data(), (size_t)N * 8);
-    put(C.o_ztiles, L.ztiles.data(), L.ztiles.size() * sizeof(int4));
     put(C.o_tb, L.tb.data(), L.tb.size() * 4);
     {
         std::atomic<size_t> next{0};
@@ -1788,79 +1647,57 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
         copy();
         for (auto& th : pool) th.join();
     }
-    // the per-tile marks: the pivot columns' diagonal tiles (their padding
-    // pivots' identity, nd_pad_pivots), then nd_mark_tiles on the device
-    memset(hp + C.o_zf, 0, (size_t)L.n_lower);
-    // (and every tile of a whole-front task: nd_factor reads those tiles as
-    // they are)
-    for (const NdDev& d : L.dev) {
-        if (d.nt <= (small_nt & 0xffff)) {
-            memset(hp + C.o_zf + d.tile_off, 1, (size_t)d.nt * (d.nt + 1) / 2);
-            continue;
-        }
-        for (int32_t K = 0; K < d.npt; ++K) hp[C.o_zf + d.tile_off + nd_lower_idx(d.nt, K, K)] = 1;
-    }
     C.ms_pack = ms_since(tp0);
     if (C.plan.bytes < total) BSM_TRY(C.plan.alloc(total));
-    BSM_HIP_TRY(hipMemcpyAsync(C.plan.p, hp, total, hipMemcpyHostToDevice, s));
-    {
-        char* pb = C.plan.as<char>();
-        uint8_t* zf = (uint8_t*)(pb + C.o_zf);
-        nd_mark_tiles<<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, (const int32_t*)(pb + C.o_pinv),
-                                                        (const int32_t*)(pb + C.o_owner), (const NdDev*)(pb + C.o_dev),
-                                                        (const int32_t*)(pb + C.o_st), zf);
-        BSM_HIP_TRY(hipGetLastError());
-        if (C.n_tiles) {
-            nd_mark_tasks<<<nd_blocks((int64_t)C.n_tiles, 256), 256, 0, s>>>((int64_t)C.n_tiles,
-                                                                             (const NdDev*)(pb + C.o_dev), zf,
-                                                                             (int4*)(pb + C.o_tiles));
-            BSM_HIP_TRY(hipGetLastError());
-        }
+    // every buffer before anything is queued: an error return afterwards
+    // would free buffers queued kernels still write, and leave the upload
+    // reading the staging buffer (the guard drains the stream)
+    DBuf cnt;  // per lower tile: A's entries' count, the fill's cursor, then the n_lower + 1 offsets
+    if (!lay.plain) {
+        BSM_TRY(cnt.alloc((size_t)(3 * C.n_lower + 1) * sizeof(int32_t), s));
+        BSM_TRY(C.aent.alloc((size_t)std::max<uint64_t>(a->nnz, 1) * sizeof(int64_t)));
+        BSM_TRY(C.tq.alloc((size_t)std::max<size_t>(C.n_tiles, 1) * sizeof(int2)));
+        BSM_TRY(C.pdesc.alloc((size_t)std::max<size_t>(C.n_tiles, 1) * 2 * sizeof(NdPull)));
     }
-    // A's entries by tile: count, scan, fill; the factor tasks' ranges (the
-    // offsets are 32-bit: a pattern with 2^31 or more lower entries keeps
-    // the zeroing and the assembly instead, BSM_ND_APULL=0's path)
-    if (a->nnz < ((uint64_t)1 << 31)) {
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{s};
+    BSM_HIP_TRY(hipMemcpyAsync(C.plan.p, hp, total, hipMemcpyHostToDevice, s));
+    // The default pipeline's lists. A's entries by tile: count, scan, fill;
+    // then the factor tasks' ranges and their children's blocks. (The offsets
+    // are 32-bit: nd_solve takes the plain pipeline for a pattern with 2^31
+    // or more entries.)
+    int32_t na = 0;
+    if (!lay.plain) {
         char* pb = C.plan.as<char>();
         const int32_t* d_pinv = (const int32_t*)(pb + C.o_pinv);
         const int32_t* d_owner = (const int32_t*)(pb + C.o_owner);
         const NdDev* d_dev = (const NdDev*)(pb + C.o_dev);
         const int32_t* d_st = (const int32_t*)(pb + C.o_st);
-        // every buffer first: an error return after a launch would free
-        // buffers queued kernels still write (and the guard drains the stream)
-        DBuf cnt;
-        BSM_TRY(cnt.alloc((size_t)std::max<int64_t>(2 * C.n_lower, 1) * sizeof(int32_t), s));
-        BSM_TRY(C.aoff.alloc((size_t)(C.n_lower + 1) * sizeof(int32_t)));
-        BSM_TRY(C.aent.alloc((size_t)std::max<uint64_t>(a->nnz, 1) * sizeof(int64_t)));
-        BSM_TRY(C.tq.alloc((size_t)std::max<size_t>(C.n_tiles, 1) * sizeof(int2)));
-        BSM_TRY(C.pdesc.alloc((size_t)std::max<size_t>(C.n_tiles, 1) * 2 * sizeof(NdPull)));
-        struct Drain {
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{s};
-        BSM_HIP_TRY(hipMemsetAsync(cnt.p, 0, (size_t)std::max<int64_t>(2 * C.n_lower, 1) * sizeof(int32_t), s));
         int32_t* d_cnt = cnt.as<int32_t>();
+        int32_t* d_aoff = d_cnt + 2 * C.n_lower;
+        BSM_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(2 * C.n_lower) * sizeof(int32_t), s));
         nd_aent_count<<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, d_pinv, d_owner, d_dev, d_st, d_cnt);
         BSM_HIP_TRY(hipGetLastError());
-        nd_scan_tiles<<<1, 1024, 0, s>>>(C.n_lower, d_cnt, C.aoff.as<int32_t>());
+        nd_scan_tiles<<<1, 1024, 0, s>>>(C.n_lower, d_cnt, d_aoff);
         BSM_HIP_TRY(hipGetLastError());
-        nd_aent_fill<<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, d_pinv, d_owner, d_dev, d_st,
-                                                       C.aoff.as<int32_t>(), d_cnt + C.n_lower, C.aent.as<int64_t>());
+        nd_aent_fill<<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, d_pinv, d_owner, d_dev, d_st, d_aoff,
+                                                       d_cnt + C.n_lower, C.aent.as<int64_t>());
         BSM_HIP_TRY(hipGetLastError());
         if (C.n_tiles) {
             nd_task_ranges<<<nd_blocks((int64_t)C.n_tiles, 256), 256, 0, s>>>(
-                (int64_t)C.n_tiles, (const int4*)(pb + C.o_tiles), d_dev, C.aoff.as<int32_t>(), C.tq.as<int2>());
+                (int64_t)C.n_tiles, (const int4*)(pb + C.o_tiles), d_dev, d_aoff, C.tq.as<int2>());
             BSM_HIP_TRY(hipGetLastError());
             nd_task_pull<<<nd_blocks((int64_t)C.n_tiles, 256), 256, 0, s>>>(
                 (int64_t)C.n_tiles, (const int4*)(pb + C.o_tiles), d_dev, (const int32_t*)(pb + C.o_tb),
                 C.pdesc.as<NdPull>());
             BSM_HIP_TRY(hipGetLastError());
         }
-        int32_t na = 0;
-        BSM_HIP_TRY(hipMemcpyAsync(&na, C.aoff.as<int32_t>() + C.n_lower, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        BSM_HIP_TRY(hipStreamSynchronize(s));  // also: the staging buffer is reused by the next plan
-        C.n_aent = na;
+        BSM_HIP_TRY(hipMemcpyAsync(&na, d_aoff + C.n_lower, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
+    BSM_HIP_TRY(hipStreamSynchronize(s));  // also: the staging buffer is reused by the next plan
+    C.n_aent = na;
     stage_mark("nd_upload", s);
     if (pre_fronts.joinable()) {  // the fronts' allocation: the wait for it as a stage of its own
         pre_fronts.join();
@@ -1872,10 +1709,10 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, int32_t small_nt, size_t es, h
 size_t nd_pattern_rp_bytes(int64_t n) { return ((size_t)(n + 1) * sizeof(int64_t) + 255) / 256 * 256; }
 
 // the pattern's key (synchronous on s: a ~6M-element pass at C5, ~10 us)
-int nd_pattern_key(const bsm_csr* a, int64_t leaf, int32_t small_nt, hipStream_t s, NdKey& key) {
+int nd_pattern_key(const bsm_csr* a, int64_t leaf, NdLay lay, bool hash_zero, hipStream_t s, NdKey& key) {
     const int64_t n = (int64_t)a->rows, total = n + 1 + (int64_t)a->nnz;
     key.device = a->device;
-    key.small_nt = small_nt;
+    key.lay = lay;
     key.n = n;
     key.leaf = leaf;
     key.nnz = a->nnz;
@@ -1889,8 +1726,7 @@ int nd_pattern_key(const bsm_csr* a, int64_t leaf, int32_t small_nt, hipStream_t
     BSM_HIP_TRY(read_dev(h, hb.p, 16, s));
     key.h0 = h[0];
     key.h1 = h[1];
-    const char* hz = getenv("BSM_ND_HASH_ZERO");  // tests: every pattern of one (n, nnz) collides
-    if (hz && atoi(hz) == 1) key.h0 = key.h1 = 0;
+    if (hash_zero) key.h0 = key.h1 = 0;  // BSM_ND_HASH_ZERO=1 (tests): every pattern of one (n, nnz) collides
     return BSM_OK;
 }
 
@@ -1955,7 +1791,8 @@ int nd_cache_find(const bsm_csr* a, const NdKey& key, hipStream_t s, std::shared
     return BSM_OK;
 }
 
-int nd_cache_insert(const bsm_csr* a, const NdKey& key, const std::shared_ptr<NdCached>& plan, hipStream_t s) {
+int nd_cache_insert(const bsm_csr* a, const NdKey& key, const std::shared_ptr<NdCached>& plan, size_t max_entries,
+                    hipStream_t s) {
     auto pat = std::make_shared<DBuf>();
     const size_t rpb = nd_pattern_rp_bytes(key.n);
     BSM_TRY(pat->alloc(rpb + (size_t)key.nnz * sizeof(int32_t)));
@@ -1975,7 +1812,7 @@ int nd_cache_insert(const bsm_csr* a, const NdKey& key, const std::shared_ptr<Nd
     e.pattern = std::move(pat);
     e.plan = plan;
     c.entries.push_back(std::move(e));
-    const size_t cap = std::max<size_t>(1, nd_cache_limit("BSM_ND_CACHE_ENTRIES", 4));
+    const size_t cap = std::max<size_t>(1, max_entries);
     while (c.entries.size() > cap) {
         auto old = std::min_element(c.entries.begin(), c.entries.end(),
                                     [](const NdCacheEntry& x, const NdCacheEntry& y) { return x.tick < y.tick; });
@@ -2011,55 +1848,41 @@ template <typename T>
 int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {
     stage_reset(s);
     const int64_t N = (int64_t)n;
-    const char* le = getenv("BSM_ND_LEAF");
-    const char* ce = getenv("BSM_ND_CACHE");
-    const char* she = getenv("BSM_ND_SHARED");
-    const int64_t leaf = le ? atoll(le) : 192;  // C5 leaf sweep: 128 / 192 / 256 / 320 -> 11.9 / 11.4 / 12.3 / 12.5 ms
-    const bool cache = !(ce && atoi(ce) == 0);
-    const bool shared = cache && !(she && atoi(she) == 0);  // the cache across handles (BSM_ND_SHARED=0: off)
-    // BSM_ND_FRONT_NT=n: fronts of at most n tile rows factor as one task
-    // each (C5: most fronts of levels 0-4 have 2-4). Default 0, every front by
-    // tiles: measured at C5, n = 3 matches it and n = 4 / 5 are 0.25 / 0.5 ms
-    // slower (a middle level's 10-15 tiles in a row on one workgroup cost more
-    // than the tickets and flags they save; profiles/r06_b_*)
-    const char* fne = getenv("BSM_ND_FRONT_NT");
-    // BSM_ND_EXT_MERGE=0: one extend launch per child slot (A/B; same bits)
-    const char* eme = getenv("BSM_ND_EXT_MERGE");
-    const bool ext_merge = !(eme && atoi(eme) == 0);
-    // the layout's options (nd_layout's `lay`): part of the plan's keys
-    // BSM_ND_LAG=u: a front's tiles below the diagonal trail its diagonal
-    // tile by u fronts' diagonals (nd_layout; 0: all diagonals of a column
-    // first, the round-5 order)
-    const char* lge = getenv("BSM_ND_LAG");
-    const int32_t lag_units = std::min(0x7ff, std::max(0, lge ? atoi(lge) : 512));
-    // BSM_ND_PULL=0: the children's update blocks added by nd_extend2 /
-    // nd_extend launches after each level (round 5) instead of inside the
-    // parent's nd_factor tiles (same bits)
-    const char* pue = getenv("BSM_ND_PULL");
-    const bool pull = !(pue && atoi(pue) == 0);
-    const int32_t small_nt =
-        (fne ? atoi(fne) : 0) | (ext_merge ? 0 : 1 << 16) | (lag_units << 17) | (pull ? 0 : 1 << 28);
+    const NdOpts opt = nd_options();
+    const bool cache = opt.cache, shared = opt.shared;
+    const int64_t leaf = opt.leaf;
+    // Two pipelines. Default: every factor tile stages its
+    // own entries of A from the plan's per-tile lists and pulls its
+    // children's update blocks through the task's descriptors, a diagonal
+    // tile skips its padding panels, and with one right-hand side the
+    // forward solve is folded into the factor. Plain (BSM_ND_PLAIN=1, and a
+    // pattern whose entries do not fit the lists' 32-bit offsets): the
+    // fronts zeroed, A assembled into them, nd_factor on F alone, one
+    // nd_extend2 launch after each level, the forward solve as its own pass.
+    // The factor has the same bits either way.
+    NdLay lay = opt.lay;
+    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);
+    const bool plain = lay.plain;
     std::shared_ptr<NdCached> pc;
     if (cache) {
         std::lock_guard<std::mutex> lk(a->plan_mu);
         auto c = std::static_pointer_cast<NdCached>(a->nd_plan);
-        if (c && c->leaf == leaf && c->small_nt == small_nt) pc = c;
+        if (c && c->leaf == leaf && c->lay == lay) pc = c;
     }
     NdKey key;
     if (pc) {
         stage_mark("nd_plan_cached", s);
     } else {
         if (shared) {
-            BSM_TRY(nd_pattern_key(a, leaf, small_nt, s, key));
+            BSM_TRY(nd_pattern_key(a, leaf, lay, opt.hash_zero, s, key));
             BSM_TRY(nd_cache_find(a, key, s, pc));
             stage_mark(pc ? "nd_plan_shared" : "nd_pattern_key", s);
         }
         if (!pc) {
             pc = std::make_shared<NdCached>();
-            const char* ke0 = getenv("BSM_ND_KEEP");
-            const bool prealloc = cache && !(ke0 && atoi(ke0) == 0);  // the fronts will be this plan's own
-            BSM_TRY(nd_build_plan(a, leaf, small_nt, prealloc ? sizeof(T) : 0, s, *pc));
-            if (shared) BSM_TRY(nd_cache_insert(a, key, pc, s));
+            // opt.keep: the fronts will be this plan's own (allocated while the layout runs)
+            BSM_TRY(nd_build_plan(a, leaf, lay, opt.threads, opt.keep ? sizeof(T) : 0, s, *pc));
+            if (shared) BSM_TRY(nd_cache_insert(a, key, pc, opt.cache_entries, s));
         }
         if (cache) {
             std::lock_guard<std::mutex> lk(a->plan_mu);
@@ -2067,12 +1890,12 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         }
     }
     NdCached& C = *pc;
-    if (getenv("BSM_ND_TRACE"))
+    if (opt.trace)
         fprintf(stderr,
                 "[bsm nd] n %lld nodes %d levels %d: graph %.1f ms, bisection %.1f ms, symbolic %.1f ms, layout "
-                "%.1f ms, packing %.1f ms; fronts %.3f GB (largest %lld), tiles %zu, extend columns %zu\n",
+                "%.1f ms, packing %.1f ms; fronts %.3f GB (largest %lld), tiles %zu, extend tasks %zu\n",
                 (long long)N, C.nn, C.n_levels, C.ms_graph, C.ms_order, C.ms_symbolic, C.ms_layout, C.ms_pack,
-                (double)C.f_elems * sizeof(T) * 1e-9, (long long)C.max_front, C.n_tiles, C.n_ext);
+                (double)C.f_elems * sizeof(T) * 1e-9, (long long)C.max_front, C.n_tiles, C.n_ext2);
     char* pb = C.plan.as<char>();
     const NdDev* d_nodes = (const NdDev*)(pb + C.o_dev);
     const int32_t* d_st = (const int32_t*)(pb + C.o_st);
@@ -2081,32 +1904,17 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     const int32_t* d_owner = (const int32_t*)(pb + C.o_owner);
     const int32_t* d_lvl = (const int32_t*)(pb + C.o_lvl);
     const int4* d_tiles = (const int4*)(pb + C.o_tiles);
-    const int4* d_ztiles = (const int4*)(pb + C.o_ztiles);
-    const int2* d_ext = (const int2*)(pb + C.o_ext);
     const int4* d_ext2 = (const int4*)(pb + C.o_ext2);
     const int2* d_ftask = (const int2*)(pb + C.o_ftask);
     const int2* d_btask = (const int2*)(pb + C.o_btask);
     const int64_t* d_perm = (const int64_t*)(pb + C.o_perm);
-    const int32_t* d_tb = pull ? (const int32_t*)(pb + C.o_tb) : nullptr;
-    // BSM_ND_ZSKIP=0: every lower tile zeroed and read (A/B; same bits). By
-    // default, with the pulled extend-add, only the tiles A's entries land in
-    const char* zse = getenv("BSM_ND_ZSKIP");
-    const int zskip = pull && !(zse && atoi(zse) == 0);
-    const uint8_t* d_zf = zskip ? (const uint8_t*)(pb + C.o_zf) : nullptr;
     // BSM_ND_FOLD=0: the forward solve as its own pass over L after the
-    // factor. By default, with one right-hand side and the pull, the
-    // factor's diagonal tiles form y and the update vectors themselves
-    // BSM_ND_APULL=0: the fronts zeroed (the marked tiles) and A assembled
-    // into them before the factor. By default, with the pull, each factor
-    // tile stages its own A entries from the plan's per-tile lists
-    const char* ape = getenv("BSM_ND_APULL");
-    const bool apull = pull && C.aent.p && !(ape && atoi(ape) == 0);
-    const char* foe = getenv("BSM_ND_FOLD");
-    const bool fold = k == 1 && pull && !(foe && atoi(foe) == 0);
+    // factor. By default, with one right-hand side, the default pipeline's
+    // diagonal tiles form y and the update vectors themselves
+    const bool fold = k == 1 && !plain && opt.fold;
     // numeric storage: the plan's own buffers when this solve may hold them
-    const char* ke = getenv("BSM_ND_KEEP");
     std::unique_lock<std::mutex> num_lock(C.num_mu, std::defer_lock);
-    const bool keep = cache && !(ke && atoi(ke) == 0) && num_lock.try_lock();
+    const bool keep = opt.keep && num_lock.try_lock();
     DBuf own_fr, own_dv, own_fl;
     DBuf& fr = keep ? C.fr : own_fr;
     DBuf& dv = keep ? C.dv : own_dv;
@@ -2114,15 +1922,9 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     const size_t fr_b = (size_t)C.f_elems * sizeof(T), dv_b = (size_t)std::max<int64_t>(C.dinv_elems, 1) * sizeof(T);
     const size_t nfl = (size_t)C.n_flags + (size_t)C.n_levels + 2;
     // a plan serves one dtype per handle; sizes match after the first solve
-    const void* fr_was = fr.p;
     BSM_TRY(nd_alloc_numeric(fr, fr_b, &C));
-    if (keep && fr.p != fr_was) C.drop_zeroed();  // reallocated: zeroed by nd_zero_tiles as usual
-    const char* poe = getenv("BSM_ND_POISON");  // tests: the fronts start as NaN (nothing may read unzeroed tiles)
-    if (poe && atoi(poe) == 1) {
-        if (C.fr_zeroed) hipStreamWaitEvent(s, C.fr_zeroed, 0);
-        C.drop_zeroed();
-        BSM_HIP_TRY(hipMemsetAsync(fr.p, 0xff, fr_b, s));
-    }
+    // BSM_ND_POISON=1 (tests): the fronts start as NaN (nothing may read unzeroed tiles)
+    if (opt.poison) BSM_HIP_TRY(hipMemsetAsync(fr.p, 0xff, fr_b, s));
     BSM_TRY(nd_alloc_numeric(dv, dv_b, &C));
     BSM_TRY(nd_alloc_numeric(fl, nfl * sizeof(int), &C));
     if (keep) C.kept_bytes = fr.bytes + dv.bytes + fl.bytes;
@@ -2140,7 +1942,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     const int64_t n_pf = (C.dinv_elems / 4096) * (int64_t)k;  // flags per pass: one per node, column, pivot tile
     const size_t n_tf = 2 * (size_t)n_pf + 2 * (size_t)C.n_levels;  // forward flags, backward flags, tickets
     DBuf bpb, vb, tfl, avb;  // from the thread's cache of temporaries (no hipFree per solve)
-    if (apull) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
+    if (!plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
     if (k > 0) {
         BSM_TRY(bpb.alloc((size_t)N * k * sizeof(T), s));
         BSM_TRY(vb.alloc((size_t)std::max<int64_t>(C.vtot, 1) * k * sizeof(T), s));
@@ -2153,42 +1955,29 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     int* d_tickets = d_flags + C.n_flags;
     int* d_status = d_tickets + C.n_levels;
     T* F = fr.as<T>();
-    if (keep && C.fr_zeroed) {  // the plan's first solve: fr is zeroed whole on another stream
-        const hipEvent_t ev = C.fr_zeroed;
-        C.fr_zeroed = nullptr;
-        const hipError_t we = hipStreamWaitEvent(s, ev, 0);
-        (void)hipEventDestroy(ev);
-        BSM_HIP_TRY(we);
-    } else if (C.n_ztiles && !apull) {
-        nd_zero_tiles<T><<<(unsigned)C.n_ztiles, 256, 0, s>>>(d_nodes, d_ztiles, F, d_zf);
-        BSM_HIP_TRY(hipGetLastError());
-    }
-    if (apull) {  // A's values in the per-tile lists' order
-        if (C.n_aent > 0) {
-            nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(),
-                                                                    static_cast<const T*>(a->vals), avb.as<T>());
+    if (plain) {
+        if (C.n_tiles) {
+            nd_zero_tiles<T><<<(unsigned)C.n_tiles, 256, 0, s>>>(d_nodes, d_tiles, F);
             BSM_HIP_TRY(hipGetLastError());
         }
-    } else {
         nd_assemble<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, static_cast<const T*>(a->vals),
                                                          d_pinv, d_owner, d_nodes, d_st, F);
         BSM_HIP_TRY(hipGetLastError());
         nd_pad_pivots<T><<<(unsigned)C.nn, 64, 0, s>>>(d_nodes, F);
         BSM_HIP_TRY(hipGetLastError());
+    } else if (C.n_aent > 0) {  // A's values in the per-tile lists' order
+        nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(),
+                                                                static_cast<const T*>(a->vals), avb.as<T>());
+        BSM_HIP_TRY(hipGetLastError());
     }
     stage_mark("nd_assemble", s);
-    const int64_t* const d_aent = apull ? C.aent.as<int64_t>() : nullptr;
-    const T* const d_av = apull ? avb.as<T>() : nullptr;
-    const int32_t* const d_aoff = apull ? C.aoff.as<int32_t>() : nullptr;
-    const int2* const d_tq = apull ? C.tq.as<int2>() : nullptr;
-    // BSM_ND_PDESC=0: the pull finds its children's blocks through the
-    // node, the child and the bounds (A/B; same bits)
-    const char* pde = getenv("BSM_ND_PDESC");
-    const NdPull* const d_pd = pull && C.pdesc.p && !(pde && atoi(pde) == 0) ? C.pdesc.as<NdPull>() : nullptr;
+    const int64_t* const d_aent = plain ? nullptr : C.aent.as<int64_t>();
+    const T* const d_av = plain ? nullptr : avb.as<T>();
+    const int2* const d_tq = plain ? nullptr : C.tq.as<int2>();
+    const NdPull* const d_pd = plain ? nullptr : C.pdesc.as<NdPull>();
     // BSM_ND_STAMPS=1: nd_factor's per-level cycle stamps, printed after the solve
-    const char* sde = getenv("BSM_ND_STAMPS");
     DBuf stamps;
-    if (sde && atoi(sde) == 1) {
+    if (opt.stamps) {
         BSM_TRY(stamps.alloc((size_t)C.n_levels * ND_NSTAMP * sizeof(unsigned long long)));
         BSM_HIP_TRY(hipMemsetAsync(stamps.p, 0, (size_t)C.n_levels * ND_NSTAMP * sizeof(unsigned long long), s));
     }
@@ -2200,37 +1989,24 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     }
     T* const fV = fold ? vb.as<T>() : nullptr;
     const T* const fbp = fold ? bpb.as<T>() : nullptr;
-    // BSM_ND_PAD_SKIP=0: diagonal tiles factor their padding panels too (A/B; same bits)
-    const char* pse = getenv("BSM_ND_PAD_SKIP");
-    const int pad_skip = !(pse && atoi(pse) == 0);
     for (int32_t lv = 0; lv < C.n_levels; ++lv) {
         const int64_t t0 = C.tiles_off[(size_t)lv], nt = C.tiles_off[(size_t)lv + 1] - t0;
         if (nt > 0) {
             const int64_t grid = std::min<int64_t>(nt, (int64_t)cus * per_cu);
             if (stamps.p)
-                nd_factor<T, true><<<(unsigned)grid, 256, 0, s>>>(d_nodes, d_tiles + t0, nt, F, dv.as<T>(), d_flags,
-                                                                  d_tickets + lv, d_status, pad_skip, d_tb, d_ri,
-                                                                  zskip, fV, fbp, d_aent, d_av, d_aoff, d_tq ? d_tq + t0 : nullptr,
-                                                                  d_pd ? d_pd + 2 * t0 : nullptr,
-                                                                  stamps.as<unsigned long long>() + ND_NSTAMP * lv);
+                nd_factor<T, true><<<(unsigned)grid, 256, 0, s>>>(
+                    d_nodes, d_tiles + t0, nt, F, dv.as<T>(), d_flags, d_tickets + lv, d_status, d_ri, fV, fbp, d_aent,
+                    d_av, d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr,
+                    stamps.as<unsigned long long>() + ND_NSTAMP * lv);
             else
                 nd_factor<T><<<(unsigned)grid, 256, 0, s>>>(d_nodes, d_tiles + t0, nt, F, dv.as<T>(), d_flags,
-                                                            d_tickets + lv, d_status, pad_skip, d_tb, d_ri, zskip,
-                                                            fV, fbp, d_aent, d_av, d_aoff, d_tq ? d_tq + t0 : nullptr,
-                                                            d_pd ? d_pd + 2 * t0 : nullptr);
+                                                            d_tickets + lv, d_status, d_ri, fV, fbp, d_aent, d_av,
+                                                            d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr);
             BSM_HIP_TRY(hipGetLastError());
         }
-        if (ext_merge && !pull) {
-            const int64_t e0 = C.ext2_off[(size_t)lv], ne = C.ext2_off[(size_t)lv + 1] - e0;
-            if (ne > 0) {
-                nd_extend2<T><<<nd_blocks(ne, 4), 256, 0, s>>>(d_nodes, d_ext2 + e0, ne, d_ri, F);
-                BSM_HIP_TRY(hipGetLastError());
-            }
-        }
-        for (int sl = 0; sl < 2 && !ext_merge && !pull; ++sl) {
-            const int64_t e0 = C.ext_off[(size_t)(2 * lv + sl)], ne = C.ext_off[(size_t)(2 * lv + sl) + 1] - e0;
-            if (ne <= 0) continue;
-            nd_extend<T><<<nd_blocks(ne, 4), 256, 0, s>>>(d_nodes, d_ext + e0, ne, d_ri, F);
+        const int64_t e0 = C.ext2_off[(size_t)lv], ne = C.ext2_off[(size_t)lv + 1] - e0;
+        if (ne > 0) {  // the plain pipeline: this level's update blocks into the parents' fronts
+            nd_extend2<T><<<nd_blocks(ne, 4), 256, 0, s>>>(d_nodes, d_ext2 + e0, ne, d_ri, F);
             BSM_HIP_TRY(hipGetLastError());
         }
     }
@@ -2246,9 +2022,6 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         // tiles on many waves), the others one workgroup per pair (nd_forward /
         // nd_backward: less bookkeeping per front). Same bits either way.
         // BSM_ND_FWD_TILES / BSM_ND_BWD_TILES = 0: never, 1: every level.
-        const char* fte = getenv("BSM_ND_FWD_TILES");
-        const char* bte = getenv("BSM_ND_BWD_TILES");
-        const int fwd_mode = fte ? atoi(fte) : 2, bwd_mode = bte ? atoi(bte) : 2;
         auto by_tiles = [&](int mode, int64_t pairs) { return mode == 1 || (mode == 2 && pairs < cus); };
         BSM_HIP_TRY(hipMemsetAsync(tfl.p, 0, n_tf * sizeof(int), s));
         int* const d_yf = tfl.as<int>();
@@ -2259,7 +2032,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         for (int32_t lv = 0; lv < C.n_levels && !fold; ++lv) {
             const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
             if (c <= 0) continue;
-            if (by_tiles(fwd_mode, c * (int64_t)k)) {
+            if (by_tiles(opt.fwd_tiles, c * (int64_t)k)) {
                 const int64_t f0 = C.ftask_off[(size_t)lv], nf = C.ftask_off[(size_t)lv + 1] - f0;
                 const int64_t grid = std::min<int64_t>(nf * (int64_t)k, fwd_grid);
                 if (grid <= 0) continue;  // fronts without rows (no pivots, no front rows)
@@ -2276,7 +2049,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
             const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
             if (c <= 0) continue;
-            if (by_tiles(bwd_mode, c * (int64_t)k)) {
+            if (by_tiles(opt.bwd_tiles, c * (int64_t)k)) {
                 const int64_t b0 = C.btask_off[(size_t)lv], nb = C.btask_off[(size_t)lv + 1] - b0;
                 const int64_t grid = std::min<int64_t>(nb * (int64_t)k, bwd_grid);
                 if (grid <= 0) continue;  // no pivots on this level
@@ -2323,7 +2096,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
                 "cholesky: matrix is not positive definite (a pivot is <= 0 or not finite)");
     if (keep && shared) {  // the cached plans' kept storage within its budget (this plan's stays)
         num_lock.unlock();
-        nd_cache_trim(nd_cache_limit("BSM_ND_CACHE_MB", 32768) << 20, &C);
+        nd_cache_trim(opt.cache_mb << 20, &C);
     }
     return BSM_OK;
 }

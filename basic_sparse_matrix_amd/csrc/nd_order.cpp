@@ -164,7 +164,6 @@ struct Bisect {
     const Graph& g;
     int64_t leaf;
     int64_t band = 0;  // max |i - j| over the edges (natural order)
-    bool band_hints = true;
     bool trace = false;
     std::deque<TNode> tree;
     std::mutex mu;
@@ -269,10 +268,8 @@ struct Bisect {
             // the halves' BFS roots: their first and last indices (a mesh's
             // far corners, where the search for a far vertex would also end
             // up), without that search's BFS
-            if (band_hints) {
-                ha = 0;
-                hb = nv - 1;
-            }
+            ha = 0;
+            hb = nv - 1;
         } else {
             lvl.assign((size_t)nv, -1);
             order.reserve((size_t)nv);
@@ -452,8 +449,6 @@ int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t le
         all.X = g.xadj.data();
         all.J = g.adj.data();
         bs.band = g.band;
-        const char* bh = getenv("BSM_ND_BANDHINT");
-        bs.band_hints = !(bh && atoi(bh) == 0);
         const char* tt = getenv("BSM_ND_TRACE");
         bs.trace = tt && atoi(tt) == 2;
         bs.run_pool({std::move(all), root, 0, -1}, threads);

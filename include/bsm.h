@@ -201,7 +201,15 @@ int bsm_solve_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void* cons
  * A's lower entries sorted by front tile (8 bytes each) and two small
  * per-task arrays. With one right-hand side (k == 1) the forward solve is
  * formed inside the factor (another summation order than k > 1, within
- * rounding; BSM_ND_FOLD=0 turns it off). The factor's other switches
+ * rounding; BSM_ND_FOLD=0 turns it off). Two pipelines: the default one
+ * (each factor tile stages its entries of A and pulls its children's update
+ * blocks itself) and, with BSM_ND_PLAIN=1, the plain one (fronts zeroed, A
+ * assembled, one extend-add launch per level, the forward solve always its
+ * own pass): the same factor bits, and the same x except that k == 1 is not
+ * folded. A pattern with nnz >= 2^31 takes the plain pipeline by itself
+ * (the default one's per-tile offsets are 32-bit), so there x for k == 1
+ * differs from the folded form in the last bits (within 1e-12 relative, the
+ * BSM_ND_FOLD tolerance); no test can run that size. The other switches
  * (README.md's table) change no bits. */
 int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols,
                  void* const* x_cols);

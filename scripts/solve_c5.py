@@ -248,9 +248,9 @@ def main():
             fms, fw, bw = st.get("nd_factor"), st.get("nd_forward"), st.get("nd_backward")
             ta, tf = roof(model["true_flops"], fms, F64_PEAK_TFS, 1e12)
             pa, pf = roof(model["padded_flops"], fms, F64_PEAK_TFS, 1e12)
-            # one right-hand side with the pull: the forward solve is folded into
-            # the factor's diagonal tiles (BSM_ND_FOLD), its stage only marks time
-            folded = os.environ.get("BSM_ND_FOLD", "1") != "0" and os.environ.get("BSM_ND_PULL", "1") != "0"
+            # one right-hand side in the default pipeline: the forward solve is folded
+            # into the factor's diagonal tiles (BSM_ND_FOLD), its stage only marks time
+            folded = os.environ.get("BSM_ND_FOLD", "1") != "0" and os.environ.get("BSM_ND_PLAIN", "0") != "1"
             fa, ff = (None, None) if folded else roof(model["l_bytes"], fw, HBM_PEAK_GBS, 1e9)
             ba, bf = roof(model["l_bytes"], bw, HBM_PEAK_GBS, 1e9)
             line.update({

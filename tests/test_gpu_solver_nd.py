@@ -278,54 +278,51 @@ def test_nd_plan_cache_bounded(orc, monkeypatch):
     assert _lib.nd_cache_info()["entries"] == 0
 
 
-@pytest.mark.parametrize("switch", ["BSM_ND_PAD_SKIP", "BSM_ND_EXT_MERGE", "BSM_ND_FWD_TILES", "BSM_ND_BWD_TILES",
-                                    "BSM_ND_FRONT_NT", "BSM_ND_LAG", "BSM_ND_PULL", "BSM_ND_ZSKIP",
-                                    "BSM_ND_APULL", "BSM_ND_PDESC"])
+# The default pipeline's shortcuts, each once a switch of its own: the cases
+# keep those names, and each now compares against the plain pipeline, which
+# takes none of them.
+PLAIN_ASPECTS = ["BSM_ND_PAD_SKIP", "BSM_ND_PULL", "BSM_ND_ZSKIP", "BSM_ND_APULL", "BSM_ND_PDESC"]
+
+
+@pytest.mark.parametrize("switch", ["BSM_ND_PLAIN", "BSM_ND_FWD_TILES", "BSM_ND_BWD_TILES", "BSM_ND_LAG"]
+                         + PLAIN_ASPECTS)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("leaf", ["8", "100", "192"])
 def test_nd_shortcuts_same_bits(orc, monkeypatch, switch, dtype, leaf):
-    """Two shortcuts that must not change a bit, each against its switch set
-    to 0 (a fresh handle per run: no cached plan or buffers shared):
-    * BSM_ND_PAD_SKIP: a front's last pivot tile ends in identity padding
-      when np is not a multiple of 64; its factor skips the padding's
-      16-column panels, which would only reproduce that identity;
-    * BSM_ND_EXT_MERGE: both children's update blocks go into the parent in
-      one launch (child 0's column, then child 1's, on one wave) instead of
-      one launch per child: the same adds in the same order;
-    * BSM_ND_FWD_TILES: the forward solve by tile rows (one wave per node,
-      tile row and column, pivot tiles' y published by flags) instead of one
-      workgroup per node and column: per row the same operations in the
-      same order;
-    * BSM_ND_BWD_TILES: the backward solve by pivot tiles (one workgroup per
-      node, pivot tile and column; the front rows' products first, then each
-      pivot tile's as its x arrives) instead of one workgroup per node and
-      column, which sums its rows in that same tile order;
-    * BSM_ND_FRONT_NT (off by default; 4 here): fronts of at most 4 tile rows
-      factored whole by one workgroup, their tiles in column order, instead
-      of one ticketed workgroup per tile: every tile the same operations in
-      the same order;
+    """Shortcuts that must not change a bit, each against its reference form
+    (a fresh handle per run: no cached plan or buffers shared):
+    * BSM_ND_PLAIN (default against =1): the default pipeline against the
+      plain one, which zeroes every lower tile, assembles A into the fronts,
+      factors each tile from F and adds the children's update blocks by one
+      nd_extend2 launch after each level. So, in one comparison (which
+      the cases named in PLAIN_ASPECTS repeat under the names of the
+      switches that each part once had):
+      - every factor tile stages its own entries of A (and the padding
+        pivots' 1) from the plan's per-tile lists, and a tile no entry lands
+        in starts from zero, neither zeroed before nor read: the same values;
+      - the children's update blocks are added inside the parent's nd_factor
+        tiles (staged in LDS, the lower-level child first, then slot 0),
+        read through per-task descriptors built once per plan: the same adds
+        in the same order;
+      - a front's last pivot tile ends in identity padding when np is not a
+        multiple of 64; its factor skips the padding's 16-column panels,
+        which (plain factors them) only reproduce that identity;
+    * BSM_ND_FWD_TILES (default against =0): the forward solve by tile rows
+      (one wave per node, tile row and column, pivot tiles' y published by
+      flags) instead of one workgroup per node and column: per row the same
+      operations in the same order;
+    * BSM_ND_BWD_TILES (default against =0): the backward solve by pivot
+      tiles (one workgroup per node, pivot tile and column; the front rows'
+      products first, then each pivot tile's as its x arrives) instead of one
+      workgroup per node and column, which sums its rows in that same tile
+      order;
     * BSM_ND_LAG (512 by default; 1 here, as this size's levels have fewer
-      fronts): a front's tiles below the diagonal taken right after the next
-      front's diagonal tile instead of after the column's last one: the same
-      tiles, only their tickets' order changes;
-    * BSM_ND_PULL: the children's update blocks added inside the parent's
-      nd_factor tiles (staged in LDS, the lower-level child first, then
-      slot 0) instead of by nd_extend2 launches after each level: the same
-      adds in the same order;
-    * BSM_ND_ZSKIP: the tiles no entry of A lands in start from zero in
-      the factor, neither zeroed before nor read, instead of zeroed and
-      read: the same values;
-    * BSM_ND_APULL: every factor tile stages its own entries of A (and the
-      padding pivots' 1) from the plan's per-tile lists, instead of the
-      fronts being zeroed and A assembled into them: the same values;
-    * BSM_ND_PDESC: the pull reads its children's blocks from per-task
-      descriptors built once per plan, instead of through the node, the
-      child and the bounds: the same blocks.
+      fronts; against =0): a front's tiles below the diagonal taken right
+      after the next front's diagonal tile instead of after the column's last
+      one: the same tiles, only their tickets' order changes.
     (At this size every level has fewer fronts than CUs, so the default runs
     the tile kernels on every level.)"""
     monkeypatch.setenv("BSM_ND_LEAF", leaf)
-    if switch == "BSM_ND_FRONT_NT":  # off by default: on (4) against off
-        monkeypatch.setenv(switch, "4")
     if switch == "BSM_ND_LAG":
         monkeypatch.setenv(switch, "1")
     g = 90
@@ -334,7 +331,10 @@ def test_nd_shortcuts_same_bits(orc, monkeypatch, switch, dtype, leaf):
     v = v.astype(dtype)
     b = orc.gen_x_cols(1013, n, 2, dtype=dtype)
     x_skip = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
-    monkeypatch.setenv(switch, "0")
+    if switch == "BSM_ND_PLAIN" or switch in PLAIN_ASPECTS:
+        monkeypatch.setenv("BSM_ND_PLAIN", "1")
+    else:
+        monkeypatch.setenv(switch, "0")
     x_full = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
     for j in range(2):
         a0, a1 = np.asarray(x_skip.get_col(j)), np.asarray(x_full.get_col(j))
@@ -345,10 +345,10 @@ def test_nd_shortcuts_same_bits(orc, monkeypatch, switch, dtype, leaf):
 @pytest.mark.parametrize("leaf", ["8", "100", "192"])
 def test_nd_poisoned_fronts_same_bits(orc, monkeypatch, dtype, leaf):
     """With the fronts filled with NaN before the solve (BSM_ND_POISON=1),
-    the default path (only the tiles A's entries land in zeroed; the others
-    start from zero in the factor and are never read) gives the bits of the
-    path that zeroes and reads every tile: nothing reads a tile it did not
-    zero or write."""
+    the default pipeline (every factor tile starts from zero and A's entries
+    in LDS; no front tile is zeroed or read before it is written) gives the
+    bits of the plain one, which zeroes and reads every tile: nothing reads a
+    tile it did not zero or write."""
     monkeypatch.setenv("BSM_ND_LEAF", leaf)
     g = 90
     n = g * g
@@ -360,7 +360,7 @@ def test_nd_poisoned_fronts_same_bits(orc, monkeypatch, dtype, leaf):
     x_p = solve(a, Dense.from_columns(b), order="nd")
     x_p2 = solve(a, Dense.from_columns(b), order="nd")  # the kept fronts, poisoned again
     monkeypatch.setenv("BSM_ND_POISON", "0")
-    monkeypatch.setenv("BSM_ND_ZSKIP", "0")
+    monkeypatch.setenv("BSM_ND_PLAIN", "1")
     x_z = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
     for j in range(2):
         a0, a1, a2 = (np.asarray(x.get_col(j)) for x in (x_p, x_p2, x_z))
@@ -400,16 +400,17 @@ def _irregular_systems(orc, kind):
 @pytest.mark.parametrize("leaf", ["4", "16", "64"])
 def test_nd_poisoned_fronts_irregular_trees(orc, monkeypatch, kind, leaf):
     """Irregular separator trees (a random graph, disconnected blocks with
-    pivot-free fronts, a 3-D mesh) with the fronts NaN-poisoned: the pulled
-    extend-add and the zero-skip give the bits of the round-5 path (the
-    extend launches, every tile zeroed and read), and x solves the system."""
+    pivot-free fronts, a 3-D mesh) with the fronts NaN-poisoned: the default
+    pipeline (the pulled extend-add, no tile zeroed) gives the bits of the
+    plain one (the extend launches, every tile zeroed and read), and x solves
+    the system."""
     n, rp, ci, v = _irregular_systems(orc, kind)
     monkeypatch.setenv("BSM_ND_LEAF", leaf)
     b = orc.gen_x_cols(1031, n, 2)
     monkeypatch.setenv("BSM_ND_POISON", "1")
     x_p = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
     monkeypatch.setenv("BSM_ND_POISON", "0")
-    monkeypatch.setenv("BSM_ND_PULL", "0")
+    monkeypatch.setenv("BSM_ND_PLAIN", "1")
     x_r = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
     ex = orc.solve(n, rp, ci, v, b, band=kind == "poisson3d")
     for j in range(2):
@@ -468,6 +469,55 @@ def test_nd_one_and_several_right_hand_sides_agree(orc, monkeypatch):
         xj = np.asarray(x3.get_col(j))
         assert rel_err(x1, xj) < 1e-12
         assert rel_err(x1, ex[j]) < 1e-10
+
+
+def test_nd_plain_one_rhs_matches_unfolded(orc, monkeypatch):
+    """What the plain pipeline means for one right-hand side: nothing is
+    folded into the factor, so BSM_ND_PLAIN=1 gives the bits of the default
+    pipeline with BSM_ND_FOLD=0 (the same factor, the same separate forward
+    pass), within 1e-10 of the band oracle."""
+    monkeypatch.setenv("BSM_ND_LEAF", "64")
+    monkeypatch.setenv("BSM_ND_CACHE", "0")
+    g = 40
+    n = g * g
+    rp, ci, v = orc.poisson2d(g)
+    b = orc.gen_x_cols(1061, n, 1)
+    monkeypatch.setenv("BSM_ND_FOLD", "0")
+    x_u = np.asarray(solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd").get_col(0))
+    monkeypatch.delenv("BSM_ND_FOLD")
+    monkeypatch.setenv("BSM_ND_PLAIN", "1")
+    x_p = np.asarray(solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd").get_col(0))
+    assert np.array_equal(x_p.view(np.uint8), x_u.view(np.uint8))
+    assert rel_err(x_p, orc.solve(n, rp, ci, v, b, band=True)[0]) < 1e-10
+
+
+def test_nd_plain_and_default_plans_do_not_mix(orc, monkeypatch):
+    """The pipeline is part of the plan's key: one pattern solved default,
+    plain, default, plain on fresh handles builds two plans (two misses of
+    the library-wide cache) and then finds each again (two hits), and all
+    four x have the same bits (two right-hand sides: with one, the default
+    pipeline folds the forward solve in and differs in the last bits)."""
+    from basic_sparse_matrix_amd import _lib
+
+    _lib.nd_cache_clear()
+    g = 24
+    n = g * g
+    rp, ci, v = orc.poisson2d(g)
+    b = orc.gen_x_cols(1062, n, 2)
+    i0 = _lib.nd_cache_info()
+    xs = []
+    for plain in (False, True, False, True):
+        if plain:
+            monkeypatch.setenv("BSM_ND_PLAIN", "1")
+        else:
+            monkeypatch.delenv("BSM_ND_PLAIN", raising=False)
+        x = solve(Csr.from_csr_arrays((n, n), rp, ci, v), Dense.from_columns(b), order="nd")
+        xs.append([np.asarray(x.get_col(j)) for j in range(2)])
+    i1 = _lib.nd_cache_info()
+    assert i1["misses"] == i0["misses"] + 2 and i1["hits"] == i0["hits"] + 2
+    for x in xs[1:]:
+        for j in range(2):
+            assert np.array_equal(x[j].view(np.uint8), xs[0][j].view(np.uint8)), j
 
 
 def poisson3d(g):
