@@ -106,6 +106,12 @@ SIGNATURES = [
     ("bsm_solve", _int, [_vp, _u64, _u64, _pp, _pp]),
     ("bsm_solve_blocked", _int, [_vp, _u64, _u64, _pp, _pp]),
     ("bsm_solve_nd", _int, [_vp, _u64, _u64, _pp, _pp]),
+    ("bsm_nd_factor_create", _int, [_vp, ctypes.POINTER(_vp)]),
+    ("bsm_nd_factor_solve", _int, [_vp, _u64, _u64, _pp, _pp]),
+    ("bsm_nd_factor_info", _int, [_vp, _u64p, ctypes.POINTER(_int), _u64p, _u64p]),
+    ("bsm_nd_factor_perm", _int, [_vp, _vp]),
+    ("bsm_nd_factor_export", _int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),
     ("bsm_nd_cache_info", _int, [_u64p, _u64p, _u64p, _u64p]),

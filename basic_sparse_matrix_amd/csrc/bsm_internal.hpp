@@ -248,6 +248,19 @@ struct bsm_csr {
 };
 
 
+// A kept nested-dissection Cholesky factor of P A P^T (kernels_nd.hip). The
+// plan (ordering, tree, device index arrays) is shared with the handles and
+// the cache that hold it; the numeric storage is the factor's own.
+struct bsm_nd_factor {
+    int dtype = BSM_F64;
+    int device = 0;
+    uint64_t n = 0;
+    std::shared_ptr<void> plan;  // NdCached; null for n == 0
+    bsm::DBuf fr, dv;            // the fronts (L in their pivot panels) and the inverse diagonal tiles
+    mutable std::mutex mu;       // one solve or export at a time
+    mutable uint64_t nnz_l = 0;  // L's stored entries, once an export has counted them (under mu)
+};
+
 namespace bsm {
 // Host-side phase times of a schedule build (bsm_mcsr_prepare's plan_ms).
 struct PlanTimes {
@@ -352,4 +365,10 @@ int solve_dispatch_full(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_
 int solve_dispatch_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
                            hipStream_t s);
 int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s);
+// the kept nd factor (kernels_nd.hip); all synchronous on s. b_dev / x_dev:
+// ROW-major n x k, as solve_dispatch_nd's
+int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s);
+int nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s);
+int nd_factor_perm(const bsm_nd_factor* f, int64_t* perm, hipStream_t s);
+int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipStream_t s);
 }  // namespace bsm

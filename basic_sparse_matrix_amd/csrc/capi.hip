@@ -1071,6 +1071,65 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
     return download_columns(a->dtype, n, k, x.p, x_cols, s);
 }
 
+// ---- the kept nd factor ----------------------------------------------------
+// the calling thread's stream, on the device the factor lives on
+static int nd_factor_stream(const bsm_nd_factor* f, hipStream_t* s) {
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return ctx_stream(s);
+}
+
+int bsm_nd_factor_create(const bsm_csr* a, bsm_nd_factor** out) {
+    BSM_REQUIRE(a && out, BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(ctx_stream(&s));  // first: without a device nothing else is answered
+    BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
+                "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
+    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
+    return nd_factor_create(a, out, s);
+}
+
+int bsm_nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* const* b_cols,
+                        void* const* x_cols) {
+    BSM_REQUIRE(f && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf b, x;
+    BSM_TRY(upload_columns(f->dtype, n, k, b_cols, b, s));
+    BSM_TRY(x.alloc(n * k * dtype_size(f->dtype)));
+    BSM_TRY(nd_factor_solve(f, k, n, b.p, x.p, s));
+    return download_columns(f->dtype, n, k, x.p, x_cols, s);
+}
+
+int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    std::lock_guard<std::mutex> lk(f->mu);
+    if (n) *n = f->n;
+    if (dtype) *dtype = f->dtype;
+    if (bytes) *bytes = (uint64_t)f->fr.bytes + (uint64_t)f->dv.bytes;
+    if (nnz_l) *nnz_l = f->nnz_l;
+    return BSM_OK;
+}
+
+int bsm_nd_factor_perm(const bsm_nd_factor* f, int64_t* perm) {
+    BSM_REQUIRE(f && (perm || f->n == 0), BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_perm(f, perm, s);
+}
+
+int bsm_nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    if (!l && !l_star) return BSM_OK;
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_export(f, l, l_star, s);
+}
+
+void bsm_nd_factor_free(bsm_nd_factor* f) { delete f; }
+
 // ---- device-level entry points --------------------------------------------
 uint64_t bsm_dev_scan_workspace_bytes(uint64_t n) {
     return ((n * sizeof(int32_t) + 255) / 256) * 256 + scan_workspace_bytes(n);

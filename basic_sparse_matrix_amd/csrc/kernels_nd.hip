@@ -1844,26 +1844,17 @@ struct NdDrainOnError {
     }
 };
 
-template <typename T>
-int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {
-    stage_reset(s);
-    const int64_t N = (int64_t)n;
-    const NdOpts opt = nd_options();
+// nd_solve's three pieces, which bsm_nd_factor (below) calls one by one: the
+// plan (nd_obtain_plan), the numeric factor (nd_stage_fronts, then
+// nd_factor_levels) and the solves (nd_solve_passes).
+
+// The plan of a's pattern: the one on the handle, else the cross-handle
+// cache's, else a new one (then kept in both, as the switches allow). es > 0:
+// a new plan allocates its kept numeric storage while it is built.
+int nd_obtain_plan(const bsm_csr* a, const NdOpts& opt, NdLay lay, size_t es, hipStream_t s,
+                   std::shared_ptr<NdCached>& pc) {
     const bool cache = opt.cache, shared = opt.shared;
     const int64_t leaf = opt.leaf;
-    // Two pipelines (DESIGN.md §4.9). Default: every factor tile stages its
-    // own entries of A from the plan's per-tile lists and pulls its
-    // children's update blocks through the task's descriptors, a diagonal
-    // tile skips its padding panels, and with one right-hand side the
-    // forward solve is folded into the factor. Plain (BSM_ND_PLAIN=1, and a
-    // pattern whose entries do not fit the lists' 32-bit offsets): the
-    // fronts zeroed, A assembled into them, nd_factor on F alone, one
-    // nd_extend2 launch after each level, the forward solve as its own pass.
-    // The factor has the same bits either way.
-    NdLay lay = opt.lay;
-    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);
-    const bool plain = lay.plain;
-    std::shared_ptr<NdCached> pc;
     if (cache) {
         std::lock_guard<std::mutex> lk(a->plan_mu);
         auto c = std::static_pointer_cast<NdCached>(a->nd_plan);
@@ -1880,8 +1871,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         }
         if (!pc) {
             pc = std::make_shared<NdCached>();
-            // opt.keep: the fronts will be this plan's own (allocated while the layout runs)
-            BSM_TRY(nd_build_plan(a, leaf, lay, opt.threads, opt.keep ? sizeof(T) : 0, s, *pc));
+            BSM_TRY(nd_build_plan(a, leaf, lay, opt.threads, es, s, *pc));
             if (shared) BSM_TRY(nd_cache_insert(a, key, pc, opt.cache_entries, s));
         }
         if (cache) {
@@ -1889,25 +1879,235 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
             a->nd_plan = pc;
         }
     }
-    NdCached& C = *pc;
+    return BSM_OK;
+}
+
+void nd_trace(const NdOpts& opt, const NdCached& C, int64_t N, size_t es) {
     if (opt.trace)
         fprintf(stderr,
                 "[bsm nd] n %lld nodes %d levels %d: graph %.1f ms, bisection %.1f ms, symbolic %.1f ms, layout "
                 "%.1f ms, packing %.1f ms; fronts %.3f GB (largest %lld), tiles %zu, extend tasks %zu\n",
                 (long long)N, C.nn, C.n_levels, C.ms_graph, C.ms_order, C.ms_symbolic, C.ms_layout, C.ms_pack,
-                (double)C.f_elems * sizeof(T) * 1e-9, (long long)C.max_front, C.n_tiles, C.n_ext2);
-    char* pb = C.plan.as<char>();
-    const NdDev* d_nodes = (const NdDev*)(pb + C.o_dev);
-    const int32_t* d_st = (const int32_t*)(pb + C.o_st);
-    const int32_t* d_ri = (const int32_t*)(pb + C.o_ri);
-    const int32_t* d_pinv = (const int32_t*)(pb + C.o_pinv);
-    const int32_t* d_owner = (const int32_t*)(pb + C.o_owner);
-    const int32_t* d_lvl = (const int32_t*)(pb + C.o_lvl);
-    const int4* d_tiles = (const int4*)(pb + C.o_tiles);
-    const int4* d_ext2 = (const int4*)(pb + C.o_ext2);
-    const int2* d_ftask = (const int2*)(pb + C.o_ftask);
-    const int2* d_btask = (const int2*)(pb + C.o_btask);
-    const int64_t* d_perm = (const int64_t*)(pb + C.o_perm);
+                (double)C.f_elems * es * 1e-9, (long long)C.max_front, C.n_tiles, C.n_ext2);
+}
+
+// the plan's device arrays
+struct NdPtrs {
+    const NdDev* nodes;
+    const int32_t *st, *ri, *pinv, *owner, *lvl;
+    const int4 *tiles, *ext2;
+    const int2 *ftask, *btask;
+    const int64_t* perm;
+};
+NdPtrs nd_ptrs(const NdCached& C) {
+    const char* pb = C.plan.as<char>();
+    NdPtrs p;
+    p.nodes = (const NdDev*)(pb + C.o_dev);
+    p.st = (const int32_t*)(pb + C.o_st);
+    p.ri = (const int32_t*)(pb + C.o_ri);
+    p.pinv = (const int32_t*)(pb + C.o_pinv);
+    p.owner = (const int32_t*)(pb + C.o_owner);
+    p.lvl = (const int32_t*)(pb + C.o_lvl);
+    p.tiles = (const int4*)(pb + C.o_tiles);
+    p.ext2 = (const int4*)(pb + C.o_ext2);
+    p.ftask = (const int2*)(pb + C.o_ftask);
+    p.btask = (const int2*)(pb + C.o_btask);
+    p.perm = (const int64_t*)(pb + C.o_perm);
+    return p;
+}
+
+// the device's CUs and the persistent kernels' workgroups per CU
+struct NdGrid {
+    int cus = 0, per_cu = 0, fper = 0, bper = 0;
+};
+template <typename T>
+int nd_grid(bool factor, bool solves, NdGrid& g) {
+    int dev = 0;
+    BSM_HIP_TRY(hipGetDevice(&dev));
+    BSM_HIP_TRY(hipDeviceGetAttribute(&g.cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (factor) {
+        BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.per_cu, nd_factor<T>, 256, 0));
+        BSM_REQUIRE(g.per_cu >= 1, BSM_ERR_UNSUPPORTED, "nd_factor does not fit a CU");
+    }
+    if (solves) {
+        BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.fper, nd_forward_tiles<T>, 64, 0));
+        BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&g.bper, nd_backward_tiles<T>, 256, 0));
+        BSM_REQUIRE(g.fper >= 1 && g.bper >= 1, BSM_ERR_UNSUPPORTED, "nd solve kernels do not fit a CU");
+    }
+    return BSM_OK;
+}
+
+// The solves' temporaries, from the thread's cache (no hipFree per solve):
+// the right-hand sides in the new order, the solve vectors, and the passes'
+// flags and tickets followed by one status word (for a solve on a kept
+// factor, whose own flags and status are gone)
+struct NdSolveTmp {
+    DBuf bpb, vb, tfl;
+    int64_t n_pf = 0;  // flags per pass: one per node, column, pivot tile
+    size_t n_tf = 0;   // forward flags, backward flags, tickets
+};
+template <typename T>
+int nd_solve_tmp(const NdCached& C, int64_t N, uint64_t k, hipStream_t s, NdSolveTmp& t) {
+    t.n_pf = (C.dinv_elems / 4096) * (int64_t)k;
+    t.n_tf = 2 * (size_t)t.n_pf + 2 * (size_t)C.n_levels;
+    BSM_TRY(t.bpb.alloc((size_t)N * k * sizeof(T), s));
+    BSM_TRY(t.vb.alloc((size_t)std::max<int64_t>(C.vtot, 1) * k * sizeof(T), s));
+    BSM_TRY(t.tfl.alloc((t.n_tf + 1) * sizeof(int), s));
+    return BSM_OK;
+}
+
+// The numeric factor, first half: the flags cleared and the fronts' input
+// staged (the plain pipeline: zeroed, A assembled, the padding pivots set; the
+// default one: A's values into the per-tile lists' order, in avb)
+template <typename T>
+int nd_stage_fronts(const bsm_csr* a, const NdCached& C, int64_t N, T* F, int* flags, size_t nfl, T* avb,
+                    hipStream_t s) {
+    const NdPtrs p = nd_ptrs(C);
+    BSM_HIP_TRY(hipMemsetAsync(flags, 0, nfl * sizeof(int), s));
+    if (C.lay.plain) {
+        if (C.n_tiles) {
+            nd_zero_tiles<T><<<(unsigned)C.n_tiles, 256, 0, s>>>(p.nodes, p.tiles, F);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        nd_assemble<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, static_cast<const T*>(a->vals),
+                                                         p.pinv, p.owner, p.nodes, p.st, F);
+        BSM_HIP_TRY(hipGetLastError());
+        nd_pad_pivots<T><<<(unsigned)C.nn, 64, 0, s>>>(p.nodes, F);
+        BSM_HIP_TRY(hipGetLastError());
+    } else if (C.n_aent > 0) {  // A's values in the per-tile lists' order
+        nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(),
+                                                                static_cast<const T*>(a->vals), avb);
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    return BSM_OK;
+}
+
+// The numeric factor, second half: nd_factor level by level (and the plain
+// pipeline's extend-add after each). flags: the tile flags, then a ticket per
+// level, then the status word. fV / fbp: the forward solve folded in (one
+// right-hand side), else null. stamps: BSM_ND_STAMPS's counters, else null.
+template <typename T>
+int nd_factor_levels(const NdCached& C, const NdGrid& g, T* F, T* Dinv, int* flags, const T* avb, T* fV,
+                     const T* fbp, unsigned long long* stamps, hipStream_t s) {
+    const NdPtrs p = nd_ptrs(C);
+    const bool plain = C.lay.plain;
+    int* const d_tickets = flags + C.n_flags;
+    int* const d_status = d_tickets + C.n_levels;
+    const int64_t* const d_aent = plain ? nullptr : C.aent.as<int64_t>();
+    const T* const d_av = plain ? nullptr : avb;
+    const int2* const d_tq = plain ? nullptr : C.tq.as<int2>();
+    const NdPull* const d_pd = plain ? nullptr : C.pdesc.as<NdPull>();
+    for (int32_t lv = 0; lv < C.n_levels; ++lv) {
+        const int64_t t0 = C.tiles_off[(size_t)lv], nt = C.tiles_off[(size_t)lv + 1] - t0;
+        if (nt > 0) {
+            const int64_t grid = std::min<int64_t>(nt, (int64_t)g.cus * g.per_cu);
+            if (stamps)
+                nd_factor<T, true><<<(unsigned)grid, 256, 0, s>>>(
+                    p.nodes, p.tiles + t0, nt, F, Dinv, flags, d_tickets + lv, d_status, p.ri, fV, fbp, d_aent, d_av,
+                    d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr, stamps + ND_NSTAMP * lv);
+            else
+                nd_factor<T><<<(unsigned)grid, 256, 0, s>>>(p.nodes, p.tiles + t0, nt, F, Dinv, flags, d_tickets + lv,
+                                                            d_status, p.ri, fV, fbp, d_aent, d_av,
+                                                            d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        const int64_t e0 = C.ext2_off[(size_t)lv], ne = C.ext2_off[(size_t)lv + 1] - e0;
+        if (ne > 0) {  // the plain pipeline: this level's update blocks into the parents' fronts
+            nd_extend2<T><<<nd_blocks(ne, 4), 256, 0, s>>>(p.nodes, p.ext2 + e0, ne, p.ri, F);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+    }
+    return BSM_OK;
+}
+
+// The solves on a finished factor (F, Dinv): b into the new order, the
+// forward levels bottom-up, the backward levels top-down, x back into A's
+// order. folded: nd_factor has formed the forward solve already (t.bpb and
+// t.vb hold its b and y), so only the backward pass runs.
+template <typename T>
+int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
+                    const T* Dinv, const void* b_dev, void* x_dev, NdSolveTmp& t, bool folded, int* d_status,
+                    hipStream_t s) {
+    const NdPtrs p = nd_ptrs(C);
+    const int cus = g.cus;
+    T* const bp = t.bpb.as<T>();
+    T* const V = t.vb.as<T>();
+    if (!folded) {
+        nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, static_cast<const T*>(b_dev), bp);
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    // Levels with fewer (node, column) pairs than CUs run their solves by
+    // tiles (nd_forward_tiles / nd_backward_tiles: a front's chain of pivot
+    // tiles on many waves), the others one workgroup per pair (nd_forward /
+    // nd_backward: less bookkeeping per front). Same bits either way.
+    // BSM_ND_FWD_TILES / BSM_ND_BWD_TILES = 0: never, 1: every level.
+    auto by_tiles = [&](int mode, int64_t pairs) { return mode == 1 || (mode == 2 && pairs < cus); };
+    BSM_HIP_TRY(hipMemsetAsync(t.tfl.p, 0, (t.n_tf + 1) * sizeof(int), s));
+    int* const d_yf = t.tfl.as<int>();
+    int* const d_xf = d_yf + t.n_pf;
+    int* const d_ftk = d_xf + t.n_pf;
+    int* const d_btk = d_ftk + C.n_levels;
+    const int64_t fwd_grid = (int64_t)cus * g.fper, bwd_grid = (int64_t)cus * g.bper;
+    for (int32_t lv = 0; lv < C.n_levels && !folded; ++lv) {
+        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
+        if (c <= 0) continue;
+        if (by_tiles(opt.fwd_tiles, c * (int64_t)k)) {
+            const int64_t f0 = C.ftask_off[(size_t)lv], nf = C.ftask_off[(size_t)lv + 1] - f0;
+            const int64_t grid = std::min<int64_t>(nf * (int64_t)k, fwd_grid);
+            if (grid <= 0) continue;  // fronts without rows (no pivots, no front rows)
+            nd_forward_tiles<T><<<(unsigned)grid, 64, 0, s>>>(p.nodes, p.ftask + f0, nf, (int)k, N, bp, V, C.vtot, F,
+                                                              Dinv, p.ri, d_yf, d_ftk + lv, d_status);
+        } else {
+            nd_forward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
+                                                                        p.ri);
+        }
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    stage_mark("nd_forward", s);
+    for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
+        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
+        if (c <= 0) continue;
+        if (by_tiles(opt.bwd_tiles, c * (int64_t)k)) {
+            const int64_t b0 = C.btask_off[(size_t)lv], nb = C.btask_off[(size_t)lv + 1] - b0;
+            const int64_t grid = std::min<int64_t>(nb * (int64_t)k, bwd_grid);
+            if (grid <= 0) continue;  // no pivots on this level
+            nd_backward_tiles<T><<<(unsigned)grid, 256, 0, s>>>(p.nodes, p.btask + b0, nb, (int)k, N, bp, V, C.vtot, F,
+                                                                Dinv, p.st, d_xf, d_btk + lv, d_status);
+        } else {
+            nd_backward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
+                                                                         p.st);
+        }
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    stage_mark("nd_backward", s);
+    nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, bp, static_cast<T*>(x_dev));
+    BSM_HIP_TRY(hipGetLastError());
+    return BSM_OK;
+}
+
+template <typename T>
+int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {
+    stage_reset(s);
+    const int64_t N = (int64_t)n;
+    const NdOpts opt = nd_options();
+    const bool shared = opt.shared;
+    // Two pipelines (DESIGN.md §4.9). Default: every factor tile stages its
+    // own entries of A from the plan's per-tile lists and pulls its
+    // children's update blocks through the task's descriptors, a diagonal
+    // tile skips its padding panels, and with one right-hand side the
+    // forward solve is folded into the factor. Plain (BSM_ND_PLAIN=1, and a
+    // pattern whose entries do not fit the lists' 32-bit offsets): the
+    // fronts zeroed, A assembled into them, nd_factor on F alone, one
+    // nd_extend2 launch after each level, the forward solve as its own pass.
+    // The factor has the same bits either way.
+    NdLay lay = opt.lay;
+    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);
+    const bool plain = lay.plain;
+    std::shared_ptr<NdCached> pc;
+    // opt.keep: the fronts will be a new plan's own (allocated while the layout runs)
+    BSM_TRY(nd_obtain_plan(a, opt, lay, opt.keep ? sizeof(T) : 0, s, pc));
+    NdCached& C = *pc;
+    nd_trace(opt, C, N, sizeof(T));
     // BSM_ND_FOLD=0: the forward solve as its own pass over L after the
     // factor. By default, with one right-hand side, the default pipeline's
     // diagonal tiles form y and the update vectors themselves
@@ -1931,50 +2131,21 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     // everything that can fail before the first launch: the occupancy
     // queries and the solves' temporaries (an error return after
     // the launches would release num_mu under running kernels)
-    int dev = 0, cus = 0, per_cu = 0, fper = 0, bper = 0;
-    BSM_HIP_TRY(hipGetDevice(&dev));
-    BSM_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nd_factor<T>, 256, 0));
-    BSM_REQUIRE(per_cu >= 1, BSM_ERR_UNSUPPORTED, "nd_factor does not fit a CU");
-    BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fper, nd_forward_tiles<T>, 64, 0));
-    BSM_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bper, nd_backward_tiles<T>, 256, 0));
-    BSM_REQUIRE(fper >= 1 && bper >= 1, BSM_ERR_UNSUPPORTED, "nd solve kernels do not fit a CU");
-    const int64_t n_pf = (C.dinv_elems / 4096) * (int64_t)k;  // flags per pass: one per node, column, pivot tile
-    const size_t n_tf = 2 * (size_t)n_pf + 2 * (size_t)C.n_levels;  // forward flags, backward flags, tickets
-    DBuf bpb, vb, tfl, avb;  // from the thread's cache of temporaries (no hipFree per solve)
+    NdGrid g;
+    BSM_TRY(nd_grid<T>(true, true, g));
+    DBuf avb;  // from the thread's cache of temporaries, as the solves' (no hipFree per solve)
+    NdSolveTmp tmp;
     if (!plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
-    if (k > 0) {
-        BSM_TRY(bpb.alloc((size_t)N * k * sizeof(T), s));
-        BSM_TRY(vb.alloc((size_t)std::max<int64_t>(C.vtot, 1) * k * sizeof(T), s));
-        BSM_TRY(tfl.alloc(n_tf * sizeof(int), s));
-    }
+    if (k > 0) BSM_TRY(nd_solve_tmp<T>(C, N, k, s, tmp));
+    DBuf& bpb = tmp.bpb;
+    DBuf& vb = tmp.vb;
     NdDrainOnError drain{s};  // destroyed before num_lock is released
     drain.armed = true;
-    BSM_HIP_TRY(hipMemsetAsync(fl.p, 0, nfl * sizeof(int), s));
     int* d_flags = fl.as<int>();
-    int* d_tickets = d_flags + C.n_flags;
-    int* d_status = d_tickets + C.n_levels;
+    int* d_status = d_flags + C.n_flags + C.n_levels;
     T* F = fr.as<T>();
-    if (plain) {
-        if (C.n_tiles) {
-            nd_zero_tiles<T><<<(unsigned)C.n_tiles, 256, 0, s>>>(d_nodes, d_tiles, F);
-            BSM_HIP_TRY(hipGetLastError());
-        }
-        nd_assemble<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, static_cast<const T*>(a->vals),
-                                                         d_pinv, d_owner, d_nodes, d_st, F);
-        BSM_HIP_TRY(hipGetLastError());
-        nd_pad_pivots<T><<<(unsigned)C.nn, 64, 0, s>>>(d_nodes, F);
-        BSM_HIP_TRY(hipGetLastError());
-    } else if (C.n_aent > 0) {  // A's values in the per-tile lists' order
-        nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(),
-                                                                static_cast<const T*>(a->vals), avb.as<T>());
-        BSM_HIP_TRY(hipGetLastError());
-    }
+    BSM_TRY(nd_stage_fronts<T>(a, C, N, F, d_flags, nfl, avb.as<T>(), s));
     stage_mark("nd_assemble", s);
-    const int64_t* const d_aent = plain ? nullptr : C.aent.as<int64_t>();
-    const T* const d_av = plain ? nullptr : avb.as<T>();
-    const int2* const d_tq = plain ? nullptr : C.tq.as<int2>();
-    const NdPull* const d_pd = plain ? nullptr : C.pdesc.as<NdPull>();
     // BSM_ND_STAMPS=1: nd_factor's per-level cycle stamps, printed after the solve
     DBuf stamps;
     if (opt.stamps) {
@@ -1982,90 +2153,16 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
         BSM_HIP_TRY(hipMemsetAsync(stamps.p, 0, (size_t)C.n_levels * ND_NSTAMP * sizeof(unsigned long long), s));
     }
     if (fold) {  // b into the new order before the factor; V's padding rows stay 0
-        nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, d_perm, static_cast<const T*>(b_dev),
+        nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, nd_ptrs(C).perm, static_cast<const T*>(b_dev),
                                                        bpb.as<T>());
         BSM_HIP_TRY(hipGetLastError());
         BSM_HIP_TRY(hipMemsetAsync(vb.p, 0, (size_t)std::max<int64_t>(C.vtot, 1) * sizeof(T), s));
     }
     T* const fV = fold ? vb.as<T>() : nullptr;
     const T* const fbp = fold ? bpb.as<T>() : nullptr;
-    for (int32_t lv = 0; lv < C.n_levels; ++lv) {
-        const int64_t t0 = C.tiles_off[(size_t)lv], nt = C.tiles_off[(size_t)lv + 1] - t0;
-        if (nt > 0) {
-            const int64_t grid = std::min<int64_t>(nt, (int64_t)cus * per_cu);
-            if (stamps.p)
-                nd_factor<T, true><<<(unsigned)grid, 256, 0, s>>>(
-                    d_nodes, d_tiles + t0, nt, F, dv.as<T>(), d_flags, d_tickets + lv, d_status, d_ri, fV, fbp, d_aent,
-                    d_av, d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr,
-                    stamps.as<unsigned long long>() + ND_NSTAMP * lv);
-            else
-                nd_factor<T><<<(unsigned)grid, 256, 0, s>>>(d_nodes, d_tiles + t0, nt, F, dv.as<T>(), d_flags,
-                                                            d_tickets + lv, d_status, d_ri, fV, fbp, d_aent, d_av,
-                                                            d_tq ? d_tq + t0 : nullptr, d_pd ? d_pd + 2 * t0 : nullptr);
-            BSM_HIP_TRY(hipGetLastError());
-        }
-        const int64_t e0 = C.ext2_off[(size_t)lv], ne = C.ext2_off[(size_t)lv + 1] - e0;
-        if (ne > 0) {  // the plain pipeline: this level's update blocks into the parents' fronts
-            nd_extend2<T><<<nd_blocks(ne, 4), 256, 0, s>>>(d_nodes, d_ext2 + e0, ne, d_ri, F);
-            BSM_HIP_TRY(hipGetLastError());
-        }
-    }
+    BSM_TRY(nd_factor_levels<T>(C, g, F, dv.as<T>(), d_flags, avb.as<T>(), fV, fbp, stamps.as<unsigned long long>(), s));
     stage_mark("nd_factor", s);
-    if (k > 0) {
-        if (!fold) {
-            nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, d_perm, static_cast<const T*>(b_dev),
-                                                           bpb.as<T>());
-            BSM_HIP_TRY(hipGetLastError());
-        }
-        // Levels with fewer (node, column) pairs than CUs run their solves by
-        // tiles (nd_forward_tiles / nd_backward_tiles: a front's chain of pivot
-        // tiles on many waves), the others one workgroup per pair (nd_forward /
-        // nd_backward: less bookkeeping per front). Same bits either way.
-        // BSM_ND_FWD_TILES / BSM_ND_BWD_TILES = 0: never, 1: every level.
-        auto by_tiles = [&](int mode, int64_t pairs) { return mode == 1 || (mode == 2 && pairs < cus); };
-        BSM_HIP_TRY(hipMemsetAsync(tfl.p, 0, n_tf * sizeof(int), s));
-        int* const d_yf = tfl.as<int>();
-        int* const d_xf = d_yf + n_pf;
-        int* const d_ftk = d_xf + n_pf;
-        int* const d_btk = d_ftk + C.n_levels;
-        const int64_t fwd_grid = (int64_t)cus * fper, bwd_grid = (int64_t)cus * bper;
-        for (int32_t lv = 0; lv < C.n_levels && !fold; ++lv) {
-            const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
-            if (c <= 0) continue;
-            if (by_tiles(opt.fwd_tiles, c * (int64_t)k)) {
-                const int64_t f0 = C.ftask_off[(size_t)lv], nf = C.ftask_off[(size_t)lv + 1] - f0;
-                const int64_t grid = std::min<int64_t>(nf * (int64_t)k, fwd_grid);
-                if (grid <= 0) continue;  // fronts without rows (no pivots, no front rows)
-                nd_forward_tiles<T><<<(unsigned)grid, 64, 0, s>>>(d_nodes, d_ftask + f0, nf, (int)k, N, bpb.as<T>(),
-                                                                  vb.as<T>(), C.vtot, F, dv.as<T>(), d_ri, d_yf,
-                                                                  d_ftk + lv, d_status);
-            } else {
-                nd_forward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(d_nodes, d_lvl + o, N, bpb.as<T>(),
-                                                                            vb.as<T>(), C.vtot, F, dv.as<T>(), d_ri);
-            }
-            BSM_HIP_TRY(hipGetLastError());
-        }
-        stage_mark("nd_forward", s);
-        for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
-            const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
-            if (c <= 0) continue;
-            if (by_tiles(opt.bwd_tiles, c * (int64_t)k)) {
-                const int64_t b0 = C.btask_off[(size_t)lv], nb = C.btask_off[(size_t)lv + 1] - b0;
-                const int64_t grid = std::min<int64_t>(nb * (int64_t)k, bwd_grid);
-                if (grid <= 0) continue;  // no pivots on this level
-                nd_backward_tiles<T><<<(unsigned)grid, 256, 0, s>>>(d_nodes, d_btask + b0, nb, (int)k, N,
-                                                                    bpb.as<T>(), vb.as<T>(), C.vtot, F, dv.as<T>(),
-                                                                    d_st, d_xf, d_btk + lv, d_status);
-            } else {
-                nd_backward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(d_nodes, d_lvl + o, N, bpb.as<T>(),
-                                                                             vb.as<T>(), C.vtot, F, dv.as<T>(), d_st);
-            }
-            BSM_HIP_TRY(hipGetLastError());
-        }
-        stage_mark("nd_backward", s);
-        nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, d_perm, bpb.as<T>(), static_cast<T*>(x_dev));
-        BSM_HIP_TRY(hipGetLastError());
-    }
+    if (k > 0) BSM_TRY(nd_solve_passes<T>(C, opt, g, N, k, F, dv.as<T>(), b_dev, x_dev, tmp, fold, d_status, s));
     int h = 0;
     BSM_HIP_TRY(read_dev(&h, d_status, sizeof(int), s));
     BSM_HIP_TRY(hipStreamSynchronize(s));
@@ -2101,7 +2198,254 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     return BSM_OK;
 }
 
+// ---- the kept factor (bsm_nd_factor) ----------------------------------------
+// The export walks L out of the fronts' pivot panels. Column c < np of a
+// front is column start + c of L (new order): front rows c .. np - 1 (L rows
+// start + r), then front rows np_pad + a, a < m (L rows st[a]); both runs
+// ascending and all >= the column, so a column of L is a row of L^T already
+// in order, the diagonal first. One wave per column, lanes striding down it
+// (contiguous in the column-major front). Never read: the padding rows and
+// columns [np, np_pad), a pivot tile above its diagonal, the update block
+// (the default pipeline leaves them undefined). Exact zeros are dropped as
+// Csr::insert drops them (sparse.rs:229); the diagonal (> 0 in a finished
+// factor) is always kept.
+
+// entry i of L's column q = nd.start + c: its value and its row in L
+template <typename T>
+__device__ __forceinline__ T nd_col_entry(const NdDev& nd, const T* __restrict__ colp, const int32_t* __restrict__ st,
+                                          int c, int i, int32_t* row) {
+    const int own = nd.np - c;  // the pivot rows c .. np - 1
+    const int fr = i < own ? c + i : nd.np_pad + (i - own);
+    *row = i < own ? (int32_t)(nd.start + c + i) : st[nd.st_off + (i - own)];
+    return colp[fr];
+}
+
+// len[q] = stored entries of column q of L (row q of L^T)
+template <typename T>
+__global__ __launch_bounds__(256) void nd_export_count(int64_t n, const int32_t* __restrict__ owner,
+                                                       const NdDev* __restrict__ nodes, const int32_t* __restrict__ st,
+                                                       const T* __restrict__ F, int32_t* __restrict__ len) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= n) return;  // wave-uniform
+    const NdDev& nd = nodes[owner[q]];
+    const int c = (int)(q - nd.start);
+    const T* const colp = F + nd.foff + (int64_t)c * nd.ld;
+    const int total = nd.np - c + nd.m;
+    int cnt = 0;
+    for (int base = 0; base < total; base += 64) {
+        const int i = base + lane;
+        bool keep = false;
+        if (i < total) {
+            int32_t row;
+            keep = i == 0 || nd_col_entry<T>(nd, colp, st, c, i, &row) != (T)0;
+        }
+        cnt += __popcll(__ballot(keep));
+    }
+    if (lane == 0) len[q] = cnt;
+}
+
+// the same walk again, writing row q of L^T at rp[q]: the place of a kept
+// entry is the wave's running offset plus the kept lanes below it
+template <typename T>
+__global__ __launch_bounds__(256) void nd_export_fill(int64_t n, const int32_t* __restrict__ owner,
+                                                      const NdDev* __restrict__ nodes, const int32_t* __restrict__ st,
+                                                      const T* __restrict__ F, const int64_t* __restrict__ rp,
+                                                      int32_t* __restrict__ col, T* __restrict__ val) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= n) return;  // wave-uniform
+    const NdDev& nd = nodes[owner[q]];
+    const int c = (int)(q - nd.start);
+    const T* const colp = F + nd.foff + (int64_t)c * nd.ld;
+    const int total = nd.np - c + nd.m;
+    int64_t run = rp[q];
+    for (int base = 0; base < total; base += 64) {
+        const int i = base + lane;
+        bool keep = false;
+        int32_t row = 0;
+        T v = (T)0;
+        if (i < total) {
+            v = nd_col_entry<T>(nd, colp, st, c, i, &row);
+            keep = i == 0 || v != (T)0;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const int64_t at = run + __popcll(mask & ((1ull << lane) - 1));
+            col[at] = row;
+            val[at] = v;
+        }
+        run += __popcll(mask);
+    }
+}
+
+template <typename T>
+int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
+    stage_reset(s);
+    const int64_t N = (int64_t)a->rows;
+    const NdOpts opt = nd_options();
+    NdLay lay = opt.lay;
+    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);  // as nd_solve
+    std::shared_ptr<NdCached> pc;
+    // no kept storage asked for on a new plan: the factor's fronts are its own
+    BSM_TRY(nd_obtain_plan(a, opt, lay, 0, s, pc));
+    NdCached& C = *pc;
+    nd_trace(opt, C, N, sizeof(T));
+    const size_t fr_b = (size_t)C.f_elems * sizeof(T), dv_b = (size_t)std::max<int64_t>(C.dinv_elems, 1) * sizeof(T);
+    const size_t nfl = (size_t)C.n_flags + (size_t)C.n_levels + 2;
+    BSM_TRY(nd_alloc_numeric(f.fr, fr_b, nullptr));
+    // BSM_ND_POISON=1 (tests): the fronts start as NaN (the export may not read what the factor did not write)
+    if (opt.poison) BSM_HIP_TRY(hipMemsetAsync(f.fr.p, 0xff, fr_b, s));
+    BSM_TRY(nd_alloc_numeric(f.dv, dv_b, nullptr));
+    NdGrid g;
+    BSM_TRY(nd_grid<T>(true, false, g));
+    DBuf fl, avb;  // temporaries: the flags, tickets and status; A's values by tile
+    BSM_TRY(fl.alloc(nfl * sizeof(int), s));
+    if (!lay.plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
+    NdDrainOnError drain{s};  // the temporaries go back to the thread's cache only after the kernels
+    drain.armed = true;
+    int* const d_flags = fl.as<int>();
+    BSM_TRY(nd_stage_fronts<T>(a, C, N, f.fr.as<T>(), d_flags, nfl, avb.as<T>(), s));
+    stage_mark("nd_assemble", s);
+    BSM_TRY(nd_factor_levels<T>(C, g, f.fr.as<T>(), f.dv.as<T>(), d_flags, avb.as<T>(), (T*)nullptr,
+                                (const T*)nullptr, nullptr, s));
+    stage_mark("nd_factor", s);
+    int h = 0;
+    BSM_HIP_TRY(read_dev(&h, d_flags + C.n_flags + C.n_levels, sizeof(int), s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    BSM_REQUIRE(!(h & ST_TIMEOUT), BSM_ERR_HIP, "nd factor: tile hand-off timed out");
+    BSM_REQUIRE(!(h & ST_NOT_PD), BSM_ERR_UNSUPPORTED,
+                "cholesky: matrix is not positive definite (a pivot is <= 0 or not finite)");
+    f.plan = pc;
+    return BSM_OK;
+}
+
+template <typename T>
+int nd_factor_solve_t(const bsm_nd_factor& f, uint64_t k, const void* b_dev, void* x_dev, hipStream_t s) {
+    stage_reset(s);
+    const int64_t N = (int64_t)f.n;
+    const NdOpts opt = nd_options();
+    const NdCached& C = *std::static_pointer_cast<NdCached>(f.plan);
+    NdGrid g;
+    BSM_TRY(nd_grid<T>(false, true, g));
+    NdSolveTmp tmp;
+    BSM_TRY(nd_solve_tmp<T>(C, N, k, s, tmp));
+    NdDrainOnError drain{s};  // the handle's mutex is released after this guard runs
+    drain.armed = true;
+    int* const d_status = tmp.tfl.as<int>() + tmp.n_tf;  // cleared with the passes' flags
+    BSM_TRY(nd_solve_passes<T>(C, opt, g, N, k, f.fr.as<T>(), f.dv.as<T>(), b_dev, x_dev, tmp, false, d_status, s));
+    int h = 0;
+    BSM_HIP_TRY(read_dev(&h, d_status, sizeof(int), s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    stage_mark("nd_copy_out", s);
+    BSM_REQUIRE(!(h & ST_TIMEOUT), BSM_ERR_HIP, "nd solve: tile hand-off timed out");
+    return BSM_OK;
+}
+
+// L^T (new order) out of the fronts: count, scan, fill
+template <typename T>
+int nd_factor_lstar_t(const bsm_nd_factor& f, bsm_csr** out, hipStream_t s) {
+    const int64_t N = (int64_t)f.n;
+    const NdCached& C = *std::static_pointer_cast<NdCached>(f.plan);
+    const NdPtrs p = nd_ptrs(C);
+    DBuf len, rp, ws;
+    const uint64_t ws_b = scan_workspace_bytes((uint64_t)N);
+    BSM_TRY(len.alloc((size_t)N * sizeof(int32_t), s));
+    BSM_TRY(rp.alloc((size_t)(N + 1) * sizeof(int64_t), s));
+    BSM_TRY(ws.alloc(ws_b, s));
+    NdDrainOnError drain{s};
+    drain.armed = true;
+    nd_export_count<T><<<nd_blocks(N, 4), 256, 0, s>>>(N, p.owner, p.nodes, p.st, f.fr.as<T>(), len.as<int32_t>());
+    BSM_HIP_TRY(hipGetLastError());
+    BSM_TRY(exclusive_scan_i32_to_i64(len.as<int32_t>(), rp.as<int64_t>(), (uint64_t)N, ws.p, ws_b, s));
+    int64_t nnz = 0;
+    BSM_HIP_TRY(read_dev(&nnz, rp.as<int64_t>() + N, sizeof(int64_t), s));
+    bsm_csr* t = nullptr;
+    BSM_TRY(csr_alloc(&t, f.dtype, (uint64_t)N, (uint64_t)N, (uint64_t)nnz));
+    hipError_t e = hipMemcpyAsync(t->row_ptr, rp.p, (size_t)(N + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) {
+        nd_export_fill<T><<<nd_blocks(N, 4), 256, 0, s>>>(N, p.owner, p.nodes, p.st, f.fr.as<T>(), t->row_ptr, t->col,
+                                                          static_cast<T*>(t->vals));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_error("nd factor export: %s", hipGetErrorString(e));
+        (void)hipStreamSynchronize(s);
+        bsm_csr_free(t);
+        return BSM_ERR_HIP;
+    }
+    drain.armed = false;
+    f.nnz_l = (uint64_t)nnz;
+    *out = t;
+    return BSM_OK;
+}
+
 }  // namespace
+
+int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s) {
+    BSM_REQUIRE(a->rows < ((uint64_t)1 << 31), BSM_ERR_UNSUPPORTED, "solve nd: n >= 2^31");
+    auto f = std::make_unique<bsm_nd_factor>();
+    f->dtype = a->dtype;
+    f->device = a->device;
+    f->n = a->rows;
+    if (a->rows > 0) {
+        int rc = BSM_ERR_INVALID;
+        if (a->dtype == BSM_F64) rc = nd_factor_create_t<double>(a, *f, s);
+        else if (a->dtype == BSM_F32) rc = nd_factor_create_t<float>(a, *f, s);
+        else set_error("solve: f32/f64 only");
+        if (rc != BSM_OK) return rc;
+    }
+    *out = f.release();
+    return BSM_OK;
+}
+
+int nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {
+    BSM_REQUIRE(f->n == n, BSM_ERR_PANIC,
+                "solve: b has %llu rows but A has %llu (index out of bounds in the reference)", (unsigned long long)n,
+                (unsigned long long)f->n);
+    if (n == 0 || k == 0) return BSM_OK;
+    std::lock_guard<std::mutex> lk(f->mu);
+    return f->dtype == BSM_F64 ? nd_factor_solve_t<double>(*f, k, b_dev, x_dev, s)
+                               : nd_factor_solve_t<float>(*f, k, b_dev, x_dev, s);
+}
+
+int nd_factor_perm(const bsm_nd_factor* f, int64_t* perm, hipStream_t s) {
+    if (f->n == 0) return BSM_OK;
+    const NdCached& C = *std::static_pointer_cast<NdCached>(f->plan);
+    BSM_HIP_TRY(hipMemcpyAsync(perm, nd_ptrs(C).perm, (size_t)f->n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    return BSM_OK;
+}
+
+int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipStream_t s) {
+    bsm_csr* ls = nullptr;
+    if (f->n == 0) {  // an empty 0 x 0 Csr: row_ptr = {0}
+        BSM_TRY(csr_alloc(&ls, f->dtype, 0, 0, 0));
+        hipError_t e = hipMemsetAsync(ls->row_ptr, 0, sizeof(int64_t), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("nd factor export: %s", hipGetErrorString(e));
+            bsm_csr_free(ls);
+            return BSM_ERR_HIP;
+        }
+    } else {
+        std::lock_guard<std::mutex> lk(f->mu);
+        BSM_TRY(f->dtype == BSM_F64 ? nd_factor_lstar_t<double>(*f, &ls, s) : nd_factor_lstar_t<float>(*f, &ls, s));
+    }
+    if (l) {  // L = (L^T)^T by the stable transpose: rows ascending, the diagonal last
+        const int rc = transpose_dispatch(ls, l, s);
+        if (rc != BSM_OK) {
+            bsm_csr_free(ls);
+            return rc;
+        }
+    }
+    if (l_star) *l_star = ls;
+    else bsm_csr_free(ls);
+    return BSM_OK;
+}
 
 // solve (lib.rs:11-24) by the nested-dissection multifrontal factorisation
 int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {

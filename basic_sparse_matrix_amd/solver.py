@@ -79,6 +79,118 @@ def solve(a: Csr, b: Dense, *, order: str = "reference") -> Dense:
     return _run(fns[order], a, b)
 
 
+class NdFactor:
+    """The nested-dissection Cholesky factor of ``P A P^T``, kept on the
+    device (``bsm_nd_factor``): factor once with :func:`cholesky_nd`, then
+    ``solve`` as often as wanted and read ``L`` out. The handle owns its
+    numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
+    end of a ``with`` block, or garbage collection. This build's addition."""
+
+    __slots__ = ("handle", "n", "dtype")
+
+    def __init__(self, handle: int):
+        lib = _lib.load()
+        self.handle = handle
+        n, d = ctypes.c_uint64(), ctypes.c_int()
+        _lib.check(lib.bsm_nd_factor_info(handle, ctypes.byref(n), ctypes.byref(d), None, None))
+        self.n = n.value
+        self.dtype = _lib.CODE_DTYPES[d.value]
+
+    def _h(self) -> int:
+        if not self.handle:
+            raise ValueError("NdFactor: used after close()")
+        return self.handle
+
+    def solve(self, b: Dense) -> Dense:
+        """``x = A^-1 b`` for the columns of ``b``: the forward and backward
+        passes only. Column ``j`` has the bits of ``solve(a, b, order="nd")``'s
+        (for one column: of that solve with ``BSM_ND_FOLD=0``)."""
+        dims = b.get_dims()
+        n, k = dims.rows, dims.cols
+        if k and b.dtype != self.dtype:
+            raise TypeError(f"NdFactor.solve: needs Dense<{self.dtype}>, got {b.dtype}")
+        b_cols = []
+        for j in range(k):
+            c = np.ascontiguousarray(b.get_col(j))
+            if c.shape[0] < n:
+                raise Panic(f"index out of bounds: the len is {c.shape[0]} but the index is {c.shape[0]}")
+            b_cols.append(np.ascontiguousarray(c[:n]))
+        lib = _lib.require_device()
+        out = Dense.new_default_with_dims(k, n, dtype=self.dtype)
+        _raise_for(lib.bsm_nd_factor_solve(self._h(), k, n, _lib.ptr_array(b_cols), _lib.ptr_array(out.data)))
+        return out
+
+    @property
+    def perm(self) -> np.ndarray:
+        """``perm[new] = old``: ``(P A P^T)[i, j] = A[perm[i], perm[j]]``."""
+        p = np.zeros(self.n, dtype=np.int64)
+        _raise_for(_lib.require_device().bsm_nd_factor_perm(self._h(), _lib.ptr(p)))
+        return p
+
+    def _export(self, want_l: bool) -> Csr:
+        lib = _lib.require_device()
+        out = ctypes.c_void_p()
+        args = (ctypes.byref(out), None) if want_l else (None, ctypes.byref(out))
+        _raise_for(lib.bsm_nd_factor_export(self._h(), *args))
+        return Csr._from_device(_lib.DeviceCsr(out.value))
+
+    def l(self) -> Csr:
+        """``L`` (new order): rows ascending, the diagonal last in each row,
+        as ``cholesky_decomp`` returns it and ``forward_substitution`` reads it."""
+        return self._export(True)
+
+    def l_star(self) -> Csr:
+        """``L^T`` (new order): the diagonal first in each row, as
+        ``backward_substitution`` reads it."""
+        return self._export(False)
+
+    def _info(self, which: int) -> int:
+        v = [ctypes.c_uint64(), ctypes.c_uint64()]
+        _lib.check(_lib.load().bsm_nd_factor_info(self._h(), None, None, ctypes.byref(v[0]), ctypes.byref(v[1])))
+        return v[which].value
+
+    @property
+    def nbytes(self) -> int:
+        """Device memory the handle owns (fronts and inverse diagonal tiles)."""
+        return self._info(0)
+
+    @property
+    def nnz_l(self) -> int:
+        """Stored entries of ``L``, or 0 until ``l()`` / ``l_star()`` has counted them."""
+        return self._info(1)
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and _lib._lib is not None:
+            _lib._lib.bsm_nd_factor_free(h)
+        self.handle = None
+
+    def __enter__(self) -> "NdFactor":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def cholesky_nd(a: Csr) -> NdFactor:
+    """Analysis (through the plan caches of ``solve(order="nd")``) and numeric
+    factorisation of ``P A P^T`` (``bsm_nd_factor_create``), kept as an
+    :class:`NdFactor`. The same type and shape checks as :func:`solve`; a
+    matrix that is not positive definite is reported here."""
+    if a.dtype not in _FLOATS:
+        raise TypeError(f"cholesky_nd: needs Csr<f32> (or f64), got {a.dtype}")
+    if a.dims.rows != a.dims.cols:
+        raise Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix")
+    dev = a._device()
+    lib = _lib.require_device()
+    out = ctypes.c_void_p()
+    _raise_for(lib.bsm_nd_factor_create(dev.handle, ctypes.byref(out)))
+    return NdFactor(out.value)
+
+
 def nd_analyse(n: int, row_ptr, col_idx, leaf: int = 256) -> dict:
     """The host analysis of ``solve(order="nd")`` on a CSR pattern
     (``bsm_nd_analyse``; no device): ``perm`` (perm[new] = old) and the

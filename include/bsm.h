@@ -213,6 +213,55 @@ int bsm_solve_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void* cons
  * (README.md's table) change no bits. */
 int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols,
                  void* const* x_cols);
+/* The factor of bsm_solve_nd, kept: factor once, solve many times, export L.
+ * This build's addition; the reference's counterpart is cholesky_decomp
+ * (sparse.rs:682-714) returning L for forward_substitution /
+ * backward_substitution (lib.rs:28-65).
+ *  - bsm_nd_factor_create: the analysis (through the plan caches above) and
+ *    the numeric factor of P A P^T. Arguments, preconditions and errors are
+ *    bsm_solve_nd's (square, f32/f64, n < 2^31, strictly increasing columns;
+ *    not positive definite -> BSM_ERR_UNSUPPORTED, reported here and not at
+ *    the first solve). No right-hand side is involved, so nothing is folded;
+ *    the factor's bits are those of bsm_solve_nd's. n == 0 gives a valid
+ *    empty factor.
+ *    Retention: the handle shares the pattern's plan (it survives
+ *    bsm_csr_free(a) and bsm_nd_cache_clear) but OWNS its numeric storage, the
+ *    fronts and the inverse diagonal tiles (~5.6 GB at C5 in f64): not the
+ *    plan's kept storage, which the next bsm_solve_nd of the pattern
+ *    overwrites. That memory is outside the BSM_ND_CACHE_MB budget, is never
+ *    dropped by the cache's trimming, is reported by bsm_nd_factor_info
+ *    (*bytes) and lives until bsm_nd_factor_free.
+ *  - bsm_nd_factor_solve: x = A^-1 b on the kept factor for k >= 0 columns
+ *    (host buffers, synchronous, as bsm_solve_nd): only the gather, the
+ *    forward levels (always the separate pass, for k == 1 too), the backward
+ *    levels and the scatter. Column j of x does not depend on k, and equals
+ *    bsm_solve_nd's column bit for bit (for k == 1: bsm_solve_nd with
+ *    BSM_ND_FOLD=0). n != rows -> BSM_ERR_PANIC. Solves on one handle from
+ *    several threads run one after the other.
+ *  - bsm_nd_factor_info: rows, dtype, device bytes the handle owns, and the
+ *    stored entries of L (0 until an export has counted them). Any pointer
+ *    may be NULL.
+ *  - bsm_nd_factor_perm: P as n entries, perm[new] = old (bsm_nd_analyse's
+ *    convention): (P A P^T)[i][j] = A[perm[i]][perm[j]].
+ *  - bsm_nd_factor_export: the factor as ordinary device Csr handles (either
+ *    pointer may be NULL; free them with bsm_csr_free), n x n in the NEW
+ *    order. *l_star = L^T: row j is column j of L, ascending, the diagonal
+ *    entry FIRST (what backward_substitution reads, lib.rs:49-65). *l = L:
+ *    rows ascending, the diagonal LAST (forward_substitution, lib.rs:28-46,
+ *    and cholesky_decomp's output convention); it is bsm_csr_transpose of
+ *    *l_star. Entries that are exactly zero are not stored (insert's rule,
+ *    sparse.rs:229); every row keeps its positive diagonal. L L^T = P A P^T
+ *    up to rounding. L with 2^32 or more entries -> BSM_ERR_UNSUPPORTED (the
+ *    transpose's limit).
+ * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
+typedef struct bsm_nd_factor bsm_nd_factor;
+int bsm_nd_factor_create(const bsm_csr* a, bsm_nd_factor** out);
+int bsm_nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* const* b_cols,
+                        void* const* x_cols);
+int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l);
+int bsm_nd_factor_perm(const bsm_nd_factor* f, int64_t* perm);
+int bsm_nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star);
+void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).
  * Any pointer may be NULL. This build's addition. */

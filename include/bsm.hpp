@@ -749,6 +749,80 @@ Dense<T> solve_nd(Csr<T> a, Dense<T> b) {
     return detail::run_solver<T>(bsm_solve_nd, a, b);
 }
 
+/// The factor of solve_nd, kept (bsm_nd_factor; this build's addition): the
+/// constructor analyses and factors P A P^T once (a non-square `a` panics,
+/// one that is not positive definite throws DeviceError), solve() runs only
+/// the forward and backward passes, l() / l_star() export the factor in
+/// cholesky_decomp's conventions (new order; perm()[new] = old). The handle
+/// owns its numeric storage (nbytes()) until it is destroyed; movable, not
+/// copyable.
+template <class T>
+    requires std::is_floating_point_v<T>
+class NdFactor {
+public:
+    explicit NdFactor(const Csr<T>& a) {
+        if (a.get_dims().rows != a.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        auto h = a.device();
+        bsm_nd_factor* f = nullptr;
+        detail::check(bsm_nd_factor_create(h.get(), &f));
+        f_.reset(f);
+        detail::check(bsm_nd_factor_info(f, &n_, nullptr, nullptr, nullptr));
+    }
+
+    size_t rows() const { return n_; }
+
+    /// x = A^-1 b: column j has the bits of solve_nd's column j (one column:
+    /// of solve_nd with BSM_ND_FOLD=0).
+    Dense<T> solve(const Dense<T>& b) const {
+        const size_t n = b.get_dims().rows, k = b.get_dims().cols;
+        Dense<T> out = Dense<T>::new_default_with_dims(k, n);
+        std::vector<const void*> in_cols(k);
+        std::vector<void*> out_cols(k);
+        for (size_t j = 0; j < k; ++j) {
+            in_cols[j] = b.get_col(j).data();
+            out_cols[j] = out.get_col_mut(j).data();
+        }
+        detail::check(bsm_nd_factor_solve(f_.get(), k, n, in_cols.data(), out_cols.data()));
+        return out;
+    }
+
+    /// perm[new] = old.
+    std::vector<int64_t> perm() const {
+        std::vector<int64_t> p(n_);
+        detail::check(bsm_nd_factor_perm(f_.get(), p.data()));
+        return p;
+    }
+
+    /// L: rows ascending, the diagonal LAST (forward_substitution's operand).
+    Csr<T> l() const {
+        bsm_csr* out = nullptr;
+        detail::check(bsm_nd_factor_export(f_.get(), &out, nullptr));
+        return Csr<T>::from_device(detail::Handle(out, detail::HandleFree{}));
+    }
+
+    /// L^T: the diagonal FIRST (backward_substitution's operand).
+    Csr<T> l_star() const {
+        bsm_csr* out = nullptr;
+        detail::check(bsm_nd_factor_export(f_.get(), nullptr, &out));
+        return Csr<T>::from_device(detail::Handle(out, detail::HandleFree{}));
+    }
+
+    /// Device bytes the handle owns.
+    uint64_t nbytes() const {
+        uint64_t b = 0;
+        detail::check(bsm_nd_factor_info(f_.get(), nullptr, nullptr, &b, nullptr));
+        return b;
+    }
+
+private:
+    struct Free {
+        void operator()(bsm_nd_factor* p) const { bsm_nd_factor_free(p); }
+    };
+    std::unique_ptr<bsm_nd_factor, Free> f_;
+    uint64_t n_ = 0;
+};
+
 }  // namespace bsm
 
 #endif  // BSM_HPP

@@ -300,6 +300,71 @@ def main():
             line["max_rel_dev_vs_oracle_x_sample"] = float(np.max(np.abs(xs - ex) / np.abs(ex)))
             line["oracle_fixture_cpu_s"] = fixture.get("cpu_seconds")
         print(json.dumps(line), flush=True)
+        if order == "nd":
+            print(json.dumps(nd_factor_line(A, B, args, by_value, line["wall_ms"], x)), flush=True)
+
+
+def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused):
+    """The kept factor (cholesky_nd / NdFactor) on the same system: host wall
+    clock around synchronous calls. factor_ms: cholesky_nd on the warm handle
+    (plan cached; the factor's own fronts allocated inside the clock);
+    solve_only_ms: the median of repeated NdFactor.solve calls on ONE factor
+    (host b in, host x out, as solve()); export_ms: bsm_nd_factor_export of
+    both L and L^T as device handles (no download). The yardsticks from the
+    same process: the fused solve by value and on the same handle."""
+    import ctypes
+
+    from basic_sparse_matrix_amd import cholesky_nd
+
+    reps = max(args.reps, 1)
+    t_factor = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f = cholesky_nd(A)
+        t_factor.append(time.perf_counter() - t0)
+        f.close()
+    f = cholesky_nd(A)
+    f.solve(B)  # warm-up: the solves' temporaries
+    t_solve, st = [], []
+    for _ in range(max(5 * reps, 10)):
+        t0 = time.perf_counter()
+        xf = f.solve(B).get_col(0)
+        t_solve.append(time.perf_counter() - t0)
+        st.append(_lib.stage_times())
+    lib = _lib.require_device()
+    t_exp, t_ls = [], []
+    for _ in range(reps + 1):  # the first one warms the export's temporaries
+        l, ls = ctypes.c_void_p(), ctypes.c_void_p()
+        t0 = time.perf_counter()
+        _lib.check(lib.bsm_nd_factor_export(f.handle, ctypes.byref(l), ctypes.byref(ls)))
+        t_exp.append(time.perf_counter() - t0)
+        lib.bsm_csr_free(l)
+        lib.bsm_csr_free(ls)
+        ls = ctypes.c_void_p()
+        t0 = time.perf_counter()
+        _lib.check(lib.bsm_nd_factor_export(f.handle, None, ctypes.byref(ls)))
+        t_ls.append(time.perf_counter() - t0)
+        lib.bsm_csr_free(ls)
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    out = {
+        "metric": "C5 nd factor object: factor once, solve many, export L (host wall ms around synchronous calls)",
+        "config": {"order": "nd", "dtype": args.dtype, "g": args.g, "rhs": 1},
+        "factor_ms": med(t_factor),
+        "solve_only_ms": med(t_solve),
+        "solve_only_ms_min_max": [round(1e3 * min(t_solve), 3), round(1e3 * max(t_solve), 3)],
+        "solve_only_calls": len(t_solve),
+        "solve_only_stages_ms": {k: round(float(np.mean([s[k] for s in st])), 3) for k in st[-1]},
+        "export_ms": med(t_exp[1:]),
+        "export_l_star_only_ms": med(t_ls[1:]),
+        "nnz_l": f.nnz_l,
+        "factor_nbytes": f.nbytes,
+        "fused_solve_by_value_call_ms": by_value["solve_call_ms"] if by_value else None,
+        "fused_solve_same_handle_wall_ms": same_handle_wall_ms,
+        "rel_dev_vs_fused_solve": float(np.linalg.norm(np.asarray(xf, np.float64) - np.asarray(x_fused, np.float64))
+                                        / np.linalg.norm(np.asarray(x_fused, np.float64))),
+    }
+    f.close()
+    return out
 
 
 if __name__ == "__main__":
