@@ -111,6 +111,10 @@ SIGNATURES = [
     ("bsm_nd_factor_info", _int, [_vp, _u64p, ctypes.POINTER(_int), _u64p, _u64p]),
     ("bsm_nd_factor_perm", _int, [_vp, _vp]),
     ("bsm_nd_factor_export", _int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    ("bsm_nd_factor_refactor", _int, [_vp, _vp]),
+    ("bsm_nd_factor_logdet", _int, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    ("bsm_nd_factor_solve_system", _int, [_vp, _int, _u64, _u64, _pp, _pp]),
+    ("bsm_dev_nd_factor_solve", _int, [_vp, _int, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),

@@ -257,8 +257,15 @@ struct bsm_nd_factor {
     uint64_t n = 0;
     std::shared_ptr<void> plan;  // NdCached; null for n == 0
     bsm::DBuf fr, dv;            // the fronts (L in their pivot panels) and the inverse diagonal tiles
-    mutable std::mutex mu;       // one solve or export at a time
+    mutable std::mutex mu;       // one solve, export, logdet or refactorisation at a time
     mutable uint64_t nnz_l = 0;  // L's stored entries, once an export has counted them (under mu)
+    // The pattern the factor was made from, which a refactorisation's matrix
+    // is compared against: row_ptr (n + 1 int64, padded to 256 bytes), then
+    // col (nnz int32), on the device. Shared with the plan cache's entry and
+    // with the other factors of the same plan while any of them lives.
+    std::shared_ptr<bsm::DBuf> pattern;
+    uint64_t nnz = 0;   // that pattern's entries
+    bool valid = true;  // false after a refactorisation that failed past its checks: fr / dv hold no factor (under mu)
 };
 
 namespace bsm {
@@ -368,7 +375,11 @@ int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_de
 // the kept nd factor (kernels_nd.hip); all synchronous on s. b_dev / x_dev:
 // ROW-major n x k, as solve_dispatch_nd's
 int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s);
-int nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s);
+// system: BSM_ND_SYS_A / _L / _LT (bsm.h)
+int nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
+                    hipStream_t s);
+int nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a, hipStream_t s);
+int nd_factor_logdet(const bsm_nd_factor* f, double* logdet, hipStream_t s);
 int nd_factor_perm(const bsm_nd_factor* f, int64_t* perm, hipStream_t s);
 int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipStream_t s);
 }  // namespace bsm

@@ -1091,16 +1091,45 @@ int bsm_nd_factor_create(const bsm_csr* a, bsm_nd_factor** out) {
     return nd_factor_create(a, out, s);
 }
 
-int bsm_nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* const* b_cols,
-                        void* const* x_cols) {
+int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* const* b_cols,
+                               void* const* x_cols) {
     BSM_REQUIRE(f && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");
     hipStream_t s;
     BSM_TRY(nd_factor_stream(f, &s));
     DBuf b, x;
     BSM_TRY(upload_columns(f->dtype, n, k, b_cols, b, s));
     BSM_TRY(x.alloc(n * k * dtype_size(f->dtype)));
-    BSM_TRY(nd_factor_solve(f, k, n, b.p, x.p, s));
+    BSM_TRY(nd_factor_solve(f, system, k, n, b.p, x.p, s));
     return download_columns(f->dtype, n, k, x.p, x_cols, s);
+}
+
+int bsm_nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* const* b_cols,
+                        void* const* x_cols) {
+    return bsm_nd_factor_solve_system(f, BSM_ND_SYS_A, k, n, b_cols, x_cols);
+}
+
+int bsm_nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a) {
+    BSM_REQUIRE(f && a, BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_refactor(f, a, s);
+}
+
+int bsm_nd_factor_logdet(const bsm_nd_factor* f, double* logdet) {
+    BSM_REQUIRE(f && logdet, BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_logdet(f, logdet, s);
+}
+
+int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, const void* b, void* x, void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(f->n * k == 0 || (b && x), BSM_ERR_INVALID, "null argument");
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return nd_factor_solve(f, system, k, f->n, b, x, static_cast<hipStream_t>(stream));
 }
 
 int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l) {

@@ -595,13 +595,14 @@ __global__ __launch_bounds__(256) void nd_extend2(const NdDev* __restrict__ node
     }
 }
 
-// right-hand sides into the new order: bp[col * n + q] = b[perm[q] * k + col] (b row-major n x k)
+// right-hand sides into the new order: bp[col * n + q] = b[perm[q] * k + col] (b row-major n x k).
+// perm == null: the identity (b is in the new order already: the L and L^T systems of a kept factor)
 template <typename T>
 __global__ __launch_bounds__(256) void nd_gather(int64_t n, int64_t k, const int64_t* __restrict__ perm,
                                                  const T* __restrict__ b, T* __restrict__ bp) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const int64_t o = perm[q];
+    const int64_t o = perm ? perm[q] : q;
     for (int64_t c = 0; c < k; ++c) bp[c * n + q] = b[o * k + c];
 }
 template <typename T>
@@ -609,8 +610,34 @@ __global__ __launch_bounds__(256) void nd_scatter(int64_t n, int64_t k, const in
                                                   const T* __restrict__ xp, T* __restrict__ x) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const int64_t o = perm[q];
+    const int64_t o = perm ? perm[q] : q;
     for (int64_t c = 0; c < k; ++c) x[o * k + c] = xp[c * n + q];
+}
+
+// The two passes of a solve hand y over in V: over the pivots of each front's
+// vector (at voff), not in bp. One pass alone (the L and L^T systems of a
+// kept factor) moves y across that boundary, one workgroup per (front,
+// column). After the forward levels: the np pivots of v out to bp.
+template <typename T>
+__global__ __launch_bounds__(256) void nd_y_out(const NdDev* __restrict__ nodes, int64_t n, const T* __restrict__ V,
+                                                int64_t vtot, T* __restrict__ bp) {
+    const NdDev& nd = nodes[blockIdx.x];
+    const int64_t col = blockIdx.y;
+    const T* const v = V + col * vtot + nd.voff;
+    for (int r = threadIdx.x; r < nd.np; r += 256) bp[col * n + nd.start + r] = v[r];
+}
+// Before the backward levels: y from bp over the pivots, and 0 over every
+// other row of the front's 64 nt: the backward kernels read whole tiles of w
+// and rely on the padding pivots and the rows past f being exactly 0 (the
+// front rows they overwrite with the ancestors' x themselves).
+template <typename T>
+__global__ __launch_bounds__(256) void nd_y_in(const NdDev* __restrict__ nodes, int64_t n, const T* __restrict__ bp,
+                                               T* __restrict__ V, int64_t vtot) {
+    const NdDev& nd = nodes[blockIdx.x];
+    const int64_t col = blockIdx.y;
+    T* const v = V + col * vtot + nd.voff;
+    const int fp = 64 * nd.nt;
+    for (int r = threadIdx.x; r < fp; r += 256) v[r] = r < nd.np ? bp[col * n + nd.start + r] : (T)0;
 }
 
 // Forward solve of one level, one workgroup per (node, column): v = the
@@ -1317,6 +1344,12 @@ struct NdCached {
     std::mutex num_mu;
     DBuf fr, dv, fl;
     std::atomic<size_t> kept_bytes{0};  // fr + dv + fl, written under num_mu
+    // The device copy of the pattern this plan was built from (row_ptr, then
+    // col, as NdCacheEntry::pattern), for whoever still holds it: the
+    // cross-handle cache's entry and the kept factors of this plan, which
+    // compare a refactorisation's matrix against it. Not owned by the plan.
+    std::mutex pat_mu;
+    std::weak_ptr<DBuf> pattern;
     // drop the kept numeric storage unless a solve holds it
     bool release_numeric() {
         std::unique_lock<std::mutex> l(num_mu, std::try_to_lock);
@@ -1791,16 +1824,28 @@ int nd_cache_find(const bsm_csr* a, const NdKey& key, hipStream_t s, std::shared
     return BSM_OK;
 }
 
-int nd_cache_insert(const bsm_csr* a, const NdKey& key, const std::shared_ptr<NdCached>& plan, size_t max_entries,
-                    hipStream_t s) {
+// A device copy of a's pattern: row_ptr (n + 1 int64, padded to 256 bytes), then col (nnz int32)
+int nd_pattern_copy(const bsm_csr* a, hipStream_t s, std::shared_ptr<DBuf>& out) {
     auto pat = std::make_shared<DBuf>();
-    const size_t rpb = nd_pattern_rp_bytes(key.n);
-    BSM_TRY(pat->alloc(rpb + (size_t)key.nnz * sizeof(int32_t)));
-    BSM_HIP_TRY(hipMemcpyAsync(pat->p, a->row_ptr, (size_t)(key.n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (key.nnz)
-        BSM_HIP_TRY(hipMemcpyAsync(pat->as<char>() + rpb, a->col, (size_t)key.nnz * sizeof(int32_t),
+    const size_t rpb = nd_pattern_rp_bytes((int64_t)a->rows);
+    BSM_TRY(pat->alloc(rpb + (size_t)a->nnz * sizeof(int32_t)));
+    BSM_HIP_TRY(hipMemcpyAsync(pat->p, a->row_ptr, (size_t)(a->rows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (a->nnz)
+        BSM_HIP_TRY(hipMemcpyAsync(pat->as<char>() + rpb, a->col, (size_t)a->nnz * sizeof(int32_t),
                                    hipMemcpyDeviceToDevice, s));
     BSM_HIP_TRY(hipStreamSynchronize(s));  // a lookup on another stream may compare against it next
+    out = std::move(pat);
+    return BSM_OK;
+}
+
+int nd_cache_insert(const bsm_csr* a, const NdKey& key, const std::shared_ptr<NdCached>& plan, size_t max_entries,
+                    hipStream_t s) {
+    std::shared_ptr<DBuf> pat;
+    BSM_TRY(nd_pattern_copy(a, s, pat));
+    {
+        std::lock_guard<std::mutex> pl(plan->pat_mu);
+        plan->pattern = pat;
+    }
     NdCache& c = nd_cache();
     std::lock_guard<std::mutex> l(c.mu);
     c.entries.erase(std::remove_if(c.entries.begin(), c.entries.end(),
@@ -2023,17 +2068,24 @@ int nd_factor_levels(const NdCached& C, const NdGrid& g, T* F, T* Dinv, int* fla
 // The solves on a finished factor (F, Dinv): b into the new order, the
 // forward levels bottom-up, the backward levels top-down, x back into A's
 // order. folded: nd_factor has formed the forward solve already (t.bpb and
-// t.vb hold its b and y), so only the backward pass runs.
+// t.vb hold its b and y), so only the backward pass runs. system (bsm.h's
+// BSM_ND_SYS_*): A, both passes; L, the forward pass alone (L y = b); LT, the
+// backward pass alone (L^T x = y), b and x then in the NEW order (no
+// permutation). Between the passes y lives in V, over each front's pivots:
+// the L system copies it out to bp after the forward levels (nd_y_out), the
+// LT system loads it from bp before the backward levels (nd_y_in).
 template <typename T>
 int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
                     const T* Dinv, const void* b_dev, void* x_dev, NdSolveTmp& t, bool folded, int* d_status,
-                    hipStream_t s) {
+                    hipStream_t s, int system = BSM_ND_SYS_A) {
     const NdPtrs p = nd_ptrs(C);
     const int cus = g.cus;
     T* const bp = t.bpb.as<T>();
     T* const V = t.vb.as<T>();
+    const bool fwd = !folded && system != BSM_ND_SYS_LT, bwd = system != BSM_ND_SYS_L;
+    const int64_t* const perm = system == BSM_ND_SYS_A ? p.perm : nullptr;
     if (!folded) {
-        nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, static_cast<const T*>(b_dev), bp);
+        nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, perm, static_cast<const T*>(b_dev), bp);
         BSM_HIP_TRY(hipGetLastError());
     }
     // Levels with fewer (node, column) pairs than CUs run their solves by
@@ -2048,7 +2100,7 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
     int* const d_ftk = d_xf + t.n_pf;
     int* const d_btk = d_ftk + C.n_levels;
     const int64_t fwd_grid = (int64_t)cus * g.fper, bwd_grid = (int64_t)cus * g.bper;
-    for (int32_t lv = 0; lv < C.n_levels && !folded; ++lv) {
+    for (int32_t lv = 0; lv < C.n_levels && fwd; ++lv) {
         const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
         if (c <= 0) continue;
         if (by_tiles(opt.fwd_tiles, c * (int64_t)k)) {
@@ -2063,8 +2115,16 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
         }
         BSM_HIP_TRY(hipGetLastError());
     }
+    if (system == BSM_ND_SYS_L && C.nn > 0) {
+        nd_y_out<T><<<dim3((unsigned)C.nn, (unsigned)k), 256, 0, s>>>(p.nodes, N, V, C.vtot, bp);
+        BSM_HIP_TRY(hipGetLastError());
+    }
     stage_mark("nd_forward", s);
-    for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
+    if (system == BSM_ND_SYS_LT && C.nn > 0) {
+        nd_y_in<T><<<dim3((unsigned)C.nn, (unsigned)k), 256, 0, s>>>(p.nodes, N, bp, V, C.vtot);
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    for (int32_t lv = C.n_levels - 1; lv >= 0 && bwd; --lv) {
         const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
         if (c <= 0) continue;
         if (by_tiles(opt.bwd_tiles, c * (int64_t)k)) {
@@ -2080,7 +2140,7 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
         BSM_HIP_TRY(hipGetLastError());
     }
     stage_mark("nd_backward", s);
-    nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, bp, static_cast<T*>(x_dev));
+    nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, perm, bp, static_cast<T*>(x_dev));
     BSM_HIP_TRY(hipGetLastError());
     return BSM_OK;
 }
@@ -2279,31 +2339,66 @@ __global__ __launch_bounds__(256) void nd_export_fill(int64_t n, const int32_t* 
     }
 }
 
+// log det A = 2 sum log L_qq over the n real pivots (a padding pivot in [np,
+// np_pad) is never read). Pass 1: a thread takes pivots q in a grid-stride
+// loop, finds the front through owner[q] and adds log of its diagonal entry
+// in f64 (for both dtypes); the wave's sum by shuffles, the workgroup's
+// through LDS: one partial per workgroup. Pass 2 (one workgroup) adds the
+// partials in index order. No floating-point atomics, and the grid depends
+// on n alone (nd_logdet_blocks), so the sum's order, hence its bits, is the
+// same on every call and every device.
+constexpr int ND_LOGDET_MAX_BLOCKS = 256;
+inline unsigned nd_logdet_blocks(int64_t n) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, ND_LOGDET_MAX_BLOCKS));
+}
 template <typename T>
-int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
-    stage_reset(s);
+__global__ __launch_bounds__(256) void nd_logdet_partial(int64_t n, const int32_t* __restrict__ owner,
+                                                         const NdDev* __restrict__ nodes, const T* __restrict__ F,
+                                                         double* __restrict__ part) {
+    __shared__ double wsum[4];
+    double acc = 0.0;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (int64_t)gridDim.x * 256) {
+        const NdDev& nd = nodes[owner[q]];
+        const int64_t c = q - nd.start;
+        acc += log((double)F[nd.foff + c * nd.ld + c]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+// out[0] = 2 (part[0] + part[1] + ... + part[nb - 1]), left to right
+__global__ __launch_bounds__(ND_LOGDET_MAX_BLOCKS) void nd_logdet_sum(int nb, const double* __restrict__ part,
+                                                                      double* __restrict__ out) {
+    __shared__ double sh[ND_LOGDET_MAX_BLOCKS];
+    if ((int)threadIdx.x < nb) sh[threadIdx.x] = part[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < nb; ++i) t += sh[i];
+        out[0] = 2.0 * t;
+    }
+}
+
+// The numeric factor of a into the handle's own fronts, on its plan C: what
+// create and refactor share. f.valid is false from the first launch until the
+// status word says the factor is whole.
+template <typename T>
+int nd_factor_numeric_t(const bsm_csr* a, bsm_nd_factor& f, const NdCached& C, const NdOpts& opt, hipStream_t s) {
     const int64_t N = (int64_t)a->rows;
-    const NdOpts opt = nd_options();
-    NdLay lay = opt.lay;
-    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);  // as nd_solve
-    std::shared_ptr<NdCached> pc;
-    // no kept storage asked for on a new plan: the factor's fronts are its own
-    BSM_TRY(nd_obtain_plan(a, opt, lay, 0, s, pc));
-    NdCached& C = *pc;
-    nd_trace(opt, C, N, sizeof(T));
-    const size_t fr_b = (size_t)C.f_elems * sizeof(T), dv_b = (size_t)std::max<int64_t>(C.dinv_elems, 1) * sizeof(T);
     const size_t nfl = (size_t)C.n_flags + (size_t)C.n_levels + 2;
-    BSM_TRY(nd_alloc_numeric(f.fr, fr_b, nullptr));
-    // BSM_ND_POISON=1 (tests): the fronts start as NaN (the export may not read what the factor did not write)
-    if (opt.poison) BSM_HIP_TRY(hipMemsetAsync(f.fr.p, 0xff, fr_b, s));
-    BSM_TRY(nd_alloc_numeric(f.dv, dv_b, nullptr));
     NdGrid g;
     BSM_TRY(nd_grid<T>(true, false, g));
     DBuf fl, avb;  // temporaries: the flags, tickets and status; A's values by tile
     BSM_TRY(fl.alloc(nfl * sizeof(int), s));
-    if (!lay.plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
+    if (!C.lay.plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
     NdDrainOnError drain{s};  // the temporaries go back to the thread's cache only after the kernels
     drain.armed = true;
+    f.valid = false;
+    f.nnz_l = 0;
+    // BSM_ND_POISON=1 (tests): the fronts start as NaN (the export may not read what the factor did not write)
+    if (opt.poison) BSM_HIP_TRY(hipMemsetAsync(f.fr.p, 0xff, f.fr.bytes, s));
     int* const d_flags = fl.as<int>();
     BSM_TRY(nd_stage_fronts<T>(a, C, N, f.fr.as<T>(), d_flags, nfl, avb.as<T>(), s));
     stage_mark("nd_assemble", s);
@@ -2317,12 +2412,98 @@ int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
     BSM_REQUIRE(!(h & ST_TIMEOUT), BSM_ERR_HIP, "nd factor: tile hand-off timed out");
     BSM_REQUIRE(!(h & ST_NOT_PD), BSM_ERR_UNSUPPORTED,
                 "cholesky: matrix is not positive definite (a pivot is <= 0 or not finite)");
-    f.plan = pc;
+    f.valid = true;
     return BSM_OK;
 }
 
 template <typename T>
-int nd_factor_solve_t(const bsm_nd_factor& f, uint64_t k, const void* b_dev, void* x_dev, hipStream_t s) {
+int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
+    stage_reset(s);
+    const int64_t N = (int64_t)a->rows;
+    const NdOpts opt = nd_options();
+    NdLay lay = opt.lay;
+    lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);  // as nd_solve
+    std::shared_ptr<NdCached> pc;
+    // no kept storage asked for on a new plan: the factor's fronts are its own
+    BSM_TRY(nd_obtain_plan(a, opt, lay, 0, s, pc));
+    NdCached& C = *pc;
+    nd_trace(opt, C, N, sizeof(T));
+    const size_t fr_b = (size_t)C.f_elems * sizeof(T), dv_b = (size_t)std::max<int64_t>(C.dinv_elems, 1) * sizeof(T);
+    BSM_TRY(nd_alloc_numeric(f.fr, fr_b, nullptr));
+    BSM_TRY(nd_alloc_numeric(f.dv, dv_b, nullptr));
+    {  // the pattern a refactorisation is compared against: the copy the plan's other holders share, else a new one
+        std::lock_guard<std::mutex> pl(C.pat_mu);
+        f.pattern = C.pattern.lock();
+        if (!f.pattern) {
+            BSM_TRY(nd_pattern_copy(a, s, f.pattern));
+            C.pattern = f.pattern;
+        }
+    }
+    f.nnz = a->nnz;
+    BSM_TRY(nd_factor_numeric_t<T>(a, f, C, opt, s));
+    f.plan = pc;
+    return BSM_OK;
+}
+
+// New values on the factor's pattern: the numeric factor again, on the
+// handle's plan and into its own storage. The caller holds f.mu.
+template <typename T>
+int nd_factor_refactor_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
+    stage_reset(s);
+    const auto pc = std::static_pointer_cast<NdCached>(f.plan);
+    const NdCached& C = *pc;
+    bool same_plan = false;  // a finalised handle's pattern never changes
+    {
+        std::lock_guard<std::mutex> lk(a->plan_mu);
+        same_plan = a->nd_plan.get() == f.plan.get();
+    }
+    if (!same_plan) {
+        const int64_t n1 = (int64_t)f.n + 1, nnz = (int64_t)f.nnz;
+        const char* pb = f.pattern->as<char>();
+        const int64_t* rpb = (const int64_t*)pb;
+        const int32_t* cb = (const int32_t*)(pb + nd_pattern_rp_bytes((int64_t)f.n));
+        DBuf db;
+        BSM_TRY(db.alloc(8, s));
+        BSM_HIP_TRY(hipMemsetAsync(db.p, 0, 8, s));
+        nd_pattern_diff<<<(unsigned)std::min<int64_t>((n1 + 255) / 256, 4096), 256, 0, s>>>(
+            a->row_ptr, rpb, n1, a->col, cb, 0, db.as<int>());
+        BSM_HIP_TRY(hipGetLastError());
+        if (nnz > 0) {
+            nd_pattern_diff<<<(unsigned)std::min<int64_t>((nnz + 255) / 256, 4096), 256, 0, s>>>(
+                a->row_ptr, rpb, 0, a->col, cb, nnz, db.as<int>() + 1);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        int diff[2] = {1, 1};
+        BSM_HIP_TRY(read_dev(diff, db.p, 8, s));
+        BSM_REQUIRE(!diff[0], BSM_ERR_INVALID, "nd factor refactor: row_ptr differs from the factored matrix's");
+        BSM_REQUIRE(!diff[1], BSM_ERR_INVALID, "nd factor refactor: col differs from the factored matrix's");
+    }
+    return nd_factor_numeric_t<T>(a, f, C, nd_options(), s);
+}
+
+template <typename T>
+int nd_factor_logdet_t(const bsm_nd_factor& f, double* logdet, hipStream_t s) {
+    const int64_t N = (int64_t)f.n;
+    const NdCached& C = *std::static_pointer_cast<NdCached>(f.plan);
+    const NdPtrs p = nd_ptrs(C);
+    const unsigned nb = nd_logdet_blocks(N);
+    DBuf part;  // the partials, then the result
+    BSM_TRY(part.alloc(((size_t)nb + 1) * sizeof(double), s));
+    NdDrainOnError drain{s};
+    drain.armed = true;
+    nd_logdet_partial<T><<<nb, 256, 0, s>>>(N, p.owner, p.nodes, f.fr.as<T>(), part.as<double>());
+    BSM_HIP_TRY(hipGetLastError());
+    nd_logdet_sum<<<1, ND_LOGDET_MAX_BLOCKS, 0, s>>>((int)nb, part.as<double>(), part.as<double>() + nb);
+    BSM_HIP_TRY(hipGetLastError());
+    double v = 0.0;
+    BSM_HIP_TRY(read_dev(&v, part.as<double>() + nb, sizeof(double), s));
+    drain.armed = false;
+    *logdet = v;
+    return BSM_OK;
+}
+
+template <typename T>
+int nd_factor_solve_t(const bsm_nd_factor& f, int system, uint64_t k, const void* b_dev, void* x_dev, hipStream_t s) {
     stage_reset(s);
     const int64_t N = (int64_t)f.n;
     const NdOpts opt = nd_options();
@@ -2334,7 +2515,8 @@ int nd_factor_solve_t(const bsm_nd_factor& f, uint64_t k, const void* b_dev, voi
     NdDrainOnError drain{s};  // the handle's mutex is released after this guard runs
     drain.armed = true;
     int* const d_status = tmp.tfl.as<int>() + tmp.n_tf;  // cleared with the passes' flags
-    BSM_TRY(nd_solve_passes<T>(C, opt, g, N, k, f.fr.as<T>(), f.dv.as<T>(), b_dev, x_dev, tmp, false, d_status, s));
+    BSM_TRY(nd_solve_passes<T>(C, opt, g, N, k, f.fr.as<T>(), f.dv.as<T>(), b_dev, x_dev, tmp, false, d_status, s,
+                               system));
     int h = 0;
     BSM_HIP_TRY(read_dev(&h, d_status, sizeof(int), s));
     BSM_HIP_TRY(hipStreamSynchronize(s));
@@ -2402,14 +2584,49 @@ int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s) {
     return BSM_OK;
 }
 
-int nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s) {
+// the state a failed refactorisation leaves behind (under f->mu)
+#define ND_REQUIRE_VALUES(f) \
+    BSM_REQUIRE((f)->valid, BSM_ERR_INVALID, "nd factor: factor holds no values; refactor first")
+
+int nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a, hipStream_t s) {
+    BSM_REQUIRE(a->device == f->device, BSM_ERR_INVALID,
+                "nd factor refactor: device differs (the matrix is on device %d, the factor on %d)", a->device,
+                f->device);
+    BSM_REQUIRE(a->dtype == f->dtype, BSM_ERR_INVALID, "nd factor refactor: dtype differs from the factored matrix's");
+    BSM_REQUIRE(a->rows == f->n && a->cols == f->n, BSM_ERR_INVALID,
+                "nd factor refactor: n differs (the matrix is %llu x %llu, the factor's %llu x %llu)",
+                (unsigned long long)a->rows, (unsigned long long)a->cols, (unsigned long long)f->n,
+                (unsigned long long)f->n);
+    if (f->n == 0) return BSM_OK;
+    BSM_REQUIRE(a->nnz == f->nnz, BSM_ERR_INVALID,
+                "nd factor refactor: nnz differs (the matrix has %llu entries, the factored one had %llu)",
+                (unsigned long long)a->nnz, (unsigned long long)f->nnz);
+    std::lock_guard<std::mutex> lk(f->mu);
+    return f->dtype == BSM_F64 ? nd_factor_refactor_t<double>(a, *f, s) : nd_factor_refactor_t<float>(a, *f, s);
+}
+
+int nd_factor_logdet(const bsm_nd_factor* f, double* logdet, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    ND_REQUIRE_VALUES(f);
+    if (f->n == 0) {
+        *logdet = 0.0;
+        return BSM_OK;
+    }
+    return f->dtype == BSM_F64 ? nd_factor_logdet_t<double>(*f, logdet, s) : nd_factor_logdet_t<float>(*f, logdet, s);
+}
+
+int nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
+                    hipStream_t s) {
+    BSM_REQUIRE(system == BSM_ND_SYS_A || system == BSM_ND_SYS_L || system == BSM_ND_SYS_LT, BSM_ERR_INVALID,
+                "nd factor solve: system must be BSM_ND_SYS_A, _L or _LT, got %d", system);
     BSM_REQUIRE(f->n == n, BSM_ERR_PANIC,
                 "solve: b has %llu rows but A has %llu (index out of bounds in the reference)", (unsigned long long)n,
                 (unsigned long long)f->n);
-    if (n == 0 || k == 0) return BSM_OK;
     std::lock_guard<std::mutex> lk(f->mu);
-    return f->dtype == BSM_F64 ? nd_factor_solve_t<double>(*f, k, b_dev, x_dev, s)
-                               : nd_factor_solve_t<float>(*f, k, b_dev, x_dev, s);
+    ND_REQUIRE_VALUES(f);
+    if (n == 0 || k == 0) return BSM_OK;
+    return f->dtype == BSM_F64 ? nd_factor_solve_t<double>(*f, system, k, b_dev, x_dev, s)
+                               : nd_factor_solve_t<float>(*f, system, k, b_dev, x_dev, s);
 }
 
 int nd_factor_perm(const bsm_nd_factor* f, int64_t* perm, hipStream_t s) {
@@ -2433,6 +2650,7 @@ int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipS
         }
     } else {
         std::lock_guard<std::mutex> lk(f->mu);
+        ND_REQUIRE_VALUES(f);
         BSM_TRY(f->dtype == BSM_F64 ? nd_factor_lstar_t<double>(*f, &ls, s) : nd_factor_lstar_t<float>(*f, &ls, s));
     }
     if (l) {  // L = (L^T)^T by the stable transpose: rows ascending, the diagonal last

@@ -166,6 +166,36 @@ def gen_dense(seed, row0, n, k, value_kind=_lib.VAL_UNIFORM, dtype=np.float64, d
     return x
 
 
+def nd_factor_solve(factor, b: torch.Tensor, out: torch.Tensor | None = None, *, system: str = "A",
+                    stream=None) -> torch.Tensor:
+    """A solve on a kept factor (``solver.NdFactor``) with ``b`` and ``x``
+    resident in HBM (``bsm_dev_nd_factor_solve``): no host copy of either.
+    ``b`` is ``(n,)`` or row-major ``(n, k)``, contiguous, of the factor's
+    dtype, on its device; ``out`` defaults to a new tensor and may be ``b``
+    (in place). ``system`` as ``NdFactor.solve``. Runs on ``stream`` and
+    returns after the solve's status word is read back; the same kernels and
+    bits as the host-buffer solve."""
+    from .solver import nd_system_code
+    from .sparse import _raise_for
+
+    code = nd_system_code(system)
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    out = torch.empty_like(b) if out is None else out
+    for name, t in (("b", b), ("out", out)):
+        if t.dtype != want:
+            raise TypeError(f"nd_factor_solve: {name} is {t.dtype}, the factor is {factor.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"nd_factor_solve: {name} is not on the device")
+        if t.dim() not in (1, 2) or t.shape[0] != factor.n or not t.is_contiguous():
+            raise ValueError(f"nd_factor_solve: {name} must be contiguous, ({factor.n},) or ({factor.n}, k), "
+                             f"got {tuple(t.shape)}")
+    if out.shape != b.shape or out.device != b.device:
+        raise ValueError(f"nd_factor_solve: out is {tuple(out.shape)} on {out.device}, b {tuple(b.shape)} on {b.device}")
+    k = b.shape[1] if b.dim() == 2 else 1
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_solve(factor._h(), code, k, _p(b), _p(out), _stream(stream)))
+    return out
+
+
 class Compactor:
     """Dense Y -> output Csr (the zero-dropping insert of sparse.rs:229) with
     preallocated worst-case buffers, so a timed step allocates nothing."""

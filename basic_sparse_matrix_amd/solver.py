@@ -79,10 +79,28 @@ def solve(a: Csr, b: Dense, *, order: str = "reference") -> Dense:
     return _run(fns[order], a, b)
 
 
+ND_SYSTEMS = {"A": 0, "L": 1, "Lt": 2}  # BSM_ND_SYS_A / _L / _LT
+
+
+def nd_system_code(system: str) -> int:
+    if system not in ND_SYSTEMS:
+        raise ValueError(f"NdFactor.solve: system must be 'A', 'L' or 'Lt', got {system!r}")
+    return ND_SYSTEMS[system]
+
+
+def _check_factorable(a: Csr, what: str):
+    if a.dtype not in _FLOATS:
+        raise TypeError(f"{what}: needs Csr<f32> (or f64), got {a.dtype}")
+    if a.dims.rows != a.dims.cols:
+        raise Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix")
+
+
 class NdFactor:
     """The nested-dissection Cholesky factor of ``P A P^T``, kept on the
     device (``bsm_nd_factor``): factor once with :func:`cholesky_nd`, then
-    ``solve`` as often as wanted and read ``L`` out. The handle owns its
+    ``solve`` as often as wanted (``A``, ``L`` or ``L^T``), read ``L`` or
+    ``logdet()`` out, and ``refactor`` new values of the same pattern in
+    place (``device.nd_factor_solve`` solves on device tensors). The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
@@ -101,10 +119,17 @@ class NdFactor:
             raise ValueError("NdFactor: used after close()")
         return self.handle
 
-    def solve(self, b: Dense) -> Dense:
+    def solve(self, b: Dense, *, system: str = "A") -> Dense:
         """``x = A^-1 b`` for the columns of ``b``: the forward and backward
         passes only. Column ``j`` has the bits of ``solve(a, b, order="nd")``'s
-        (for one column: of that solve with ``BSM_ND_FOLD=0``)."""
+        (for one column: of that solve with ``BSM_ND_FOLD=0``).
+
+        ``system="L"`` solves ``L y = b`` (the forward pass alone) and
+        ``system="Lt"`` solves ``L^T x = y`` (the backward pass alone), with
+        ``b``, ``y`` and ``x`` in the NEW order (``perm``, ``l()``): nothing
+        is permuted, so ``x[perm] = Lt(L(b[perm]))`` has the bits of
+        ``system="A"``."""
+        sys_code = nd_system_code(system)
         dims = b.get_dims()
         n, k = dims.rows, dims.cols
         if k and b.dtype != self.dtype:
@@ -117,8 +142,32 @@ class NdFactor:
             b_cols.append(np.ascontiguousarray(c[:n]))
         lib = _lib.require_device()
         out = Dense.new_default_with_dims(k, n, dtype=self.dtype)
-        _raise_for(lib.bsm_nd_factor_solve(self._h(), k, n, _lib.ptr_array(b_cols), _lib.ptr_array(out.data)))
+        _raise_for(lib.bsm_nd_factor_solve_system(self._h(), sys_code, k, n, _lib.ptr_array(b_cols),
+                                                  _lib.ptr_array(out.data)))
         return out
+
+    def refactor(self, a: Csr) -> None:
+        """New values on the same pattern (``bsm_nd_factor_refactor``): the
+        numeric factor alone, into this handle's storage, on the plan fixed
+        when the factor was made. Afterwards the factor has the bits of
+        ``cholesky_nd(a)``. ``a`` must have the factored matrix's dtype, shape
+        and pattern (else the error for ``BSM_ERR_INVALID``, the factor
+        untouched). Values that are not positive definite raise as
+        :func:`cholesky_nd` does and leave the handle WITHOUT a factor: until
+        a later ``refactor`` succeeds, ``solve``, ``l()``, ``l_star()`` and
+        ``logdet()`` raise; ``perm`` and ``nbytes`` still answer."""
+        _check_factorable(a, "NdFactor.refactor")
+        h = self._h()
+        dev = a._device()
+        _raise_for(_lib.require_device().bsm_nd_factor_refactor(h, dev.handle))
+
+    def logdet(self) -> float:
+        """``log det A = 2 sum log L_ii`` (``bsm_nd_factor_logdet``), summed in
+        f64 in a fixed order: the same bits on every call."""
+        h = self._h()
+        v = ctypes.c_double()
+        _raise_for(_lib.require_device().bsm_nd_factor_logdet(h, ctypes.byref(v)))
+        return v.value
 
     @property
     def perm(self) -> np.ndarray:
@@ -180,10 +229,7 @@ def cholesky_nd(a: Csr) -> NdFactor:
     factorisation of ``P A P^T`` (``bsm_nd_factor_create``), kept as an
     :class:`NdFactor`. The same type and shape checks as :func:`solve`; a
     matrix that is not positive definite is reported here."""
-    if a.dtype not in _FLOATS:
-        raise TypeError(f"cholesky_nd: needs Csr<f32> (or f64), got {a.dtype}")
-    if a.dims.rows != a.dims.cols:
-        raise Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix")
+    _check_factorable(a, "cholesky_nd")
     dev = a._device()
     lib = _lib.require_device()
     out = ctypes.c_void_p()

@@ -253,14 +253,60 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    sparse.rs:229); every row keeps its positive diagonal. L L^T = P A P^T
  *    up to rounding. L with 2^32 or more entries -> BSM_ERR_UNSUPPORTED (the
  *    transpose's limit).
+ *  - bsm_nd_factor_refactor: new values on the same pattern (Newton steps,
+ *    time stepping): the numeric factor alone, on the handle's plan and into
+ *    its own storage; no analysis, no cache lookup, no allocation of fronts.
+ *    The plan was fixed at create time: BSM_ND_LEAF / _PLAIN / _LAG are not
+ *    read again. `a` must be the factored matrix with other values: same
+ *    device, dtype, n, nnz, row_ptr and col, which the factor checks itself
+ *    against the device copy of the pattern it keeps (the plan cache may be
+ *    off or cleared). Any difference -> BSM_ERR_INVALID naming the field, the
+ *    factor untouched. On success the factor is, bit for bit, what
+ *    bsm_nd_factor_create(a) gives, and nnz_l is 0 again. Values that are not
+ *    positive definite -> BSM_ERR_UNSUPPORTED (a hand-off timeout ->
+ *    BSM_ERR_HIP); the old factor is overwritten by then, so the handle holds
+ *    NO factor: solve, solve_system, the device solve, export and logdet
+ *    return BSM_ERR_INVALID ("factor holds no values; refactor first") until
+ *    a later refactor succeeds; info, perm and free keep working. n == 0:
+ *    BSM_OK, nothing done. Solves and exports on other threads run before or
+ *    after a refactorisation, never during it.
+ *    The pattern copy (8 (n + 1) + 4 nnz bytes, 28 MB at C5) is shared by the
+ *    plan cache's entry and every factor of the plan, and freed with the last
+ *    of them; bsm_nd_factor_info's *bytes does NOT count it.
+ *  - bsm_nd_factor_logdet: log det A = 2 sum log L_qq over the n pivots,
+ *    summed in f64 (for f32 too) in a fixed order that depends on n alone:
+ *    the same bits on every call and device. Synchronous. n == 0 -> 0.0.
+ *  - bsm_nd_factor_solve_system: bsm_nd_factor_solve's arguments and errors,
+ *    plus the system. BSM_ND_SYS_A: bsm_nd_factor_solve itself. BSM_ND_SYS_L:
+ *    L y = b, the forward levels alone; BSM_ND_SYS_LT: L^T x = y, the backward
+ *    levels alone. For L and LT, b, y and x are in the NEW order (the order
+ *    of bsm_nd_factor_export and bsm_nd_factor_perm; nothing is permuted),
+ *    so x = P^T LT(L(P b)) has the bits of BSM_ND_SYS_A's x. Another system
+ *    value -> BSM_ERR_INVALID.
+ *  - bsm_dev_nd_factor_solve: the same solve with b and x in HBM on the
+ *    factor's device, ROW-major n x k (bsm_dev_spmm's X and Y), on `stream`;
+ *    x == b is allowed. No host copy of b or x and no allocation beyond the
+ *    calling thread's cached solve temporaries. It returns after the status
+ *    word is read back: synchronous for that stream. The same kernels, hence
+ *    the same bits, as the host call. A null pointer with n k > 0 ->
+ *    BSM_ERR_INVALID.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
+#define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
+#define BSM_ND_SYS_L 1  /* L y = b (new order) */
+#define BSM_ND_SYS_LT 2 /* L^T x = y (new order) */
 int bsm_nd_factor_create(const bsm_csr* a, bsm_nd_factor** out);
 int bsm_nd_factor_solve(const bsm_nd_factor* f, uint64_t k, uint64_t n, const void* const* b_cols,
                         void* const* x_cols);
 int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l);
 int bsm_nd_factor_perm(const bsm_nd_factor* f, int64_t* perm);
 int bsm_nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star);
+int bsm_nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a);
+int bsm_nd_factor_logdet(const bsm_nd_factor* f, double* logdet);
+int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n,
+                               const void* const* b_cols, void* const* x_cols);
+int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, const void* b, void* x,
+                            void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

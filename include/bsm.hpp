@@ -749,6 +749,9 @@ Dense<T> solve_nd(Csr<T> a, Dense<T> b) {
     return detail::run_solver<T>(bsm_solve_nd, a, b);
 }
 
+/// The system an NdFactor solves (BSM_ND_SYS_*).
+enum class NdSystem : int { A = BSM_ND_SYS_A, L = BSM_ND_SYS_L, Lt = BSM_ND_SYS_LT };
+
 /// The factor of solve_nd, kept (bsm_nd_factor; this build's addition): the
 /// constructor analyses and factors P A P^T once (a non-square `a` panics,
 /// one that is not positive definite throws DeviceError), solve() runs only
@@ -772,9 +775,29 @@ public:
 
     size_t rows() const { return n_; }
 
+    /// New values on the same pattern (bsm_nd_factor_refactor): afterwards the
+    /// factor has the bits of NdFactor(a). Another dtype is a compile error;
+    /// another shape or pattern throws and leaves the factor untouched. Values
+    /// that are not positive definite throw DeviceError and leave the handle
+    /// without a factor until a later refactor succeeds.
+    void refactor(const Csr<T>& a) {
+        if (a.get_dims().rows != a.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        auto h = a.device();
+        detail::check(bsm_nd_factor_refactor(f_.get(), h.get()));
+    }
+
+    /// log det A = 2 sum log L_ii, summed in f64 in a fixed order.
+    double logdet() const {
+        double v = 0.0;
+        detail::check(bsm_nd_factor_logdet(f_.get(), &v));
+        return v;
+    }
+
     /// x = A^-1 b: column j has the bits of solve_nd's column j (one column:
-    /// of solve_nd with BSM_ND_FOLD=0).
-    Dense<T> solve(const Dense<T>& b) const {
+    /// of solve_nd with BSM_ND_FOLD=0). NdSystem::L: L y = b; NdSystem::Lt:
+    /// L^T x = y, both in the NEW order (perm(), l()): nothing is permuted.
+    Dense<T> solve(const Dense<T>& b, NdSystem system = NdSystem::A) const {
         const size_t n = b.get_dims().rows, k = b.get_dims().cols;
         Dense<T> out = Dense<T>::new_default_with_dims(k, n);
         std::vector<const void*> in_cols(k);
@@ -783,7 +806,8 @@ public:
             in_cols[j] = b.get_col(j).data();
             out_cols[j] = out.get_col_mut(j).data();
         }
-        detail::check(bsm_nd_factor_solve(f_.get(), k, n, in_cols.data(), out_cols.data()));
+        detail::check(bsm_nd_factor_solve_system(f_.get(), static_cast<int>(system), k, n, in_cols.data(),
+                                                 out_cols.data()));
         return out;
     }
 

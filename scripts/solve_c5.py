@@ -301,17 +301,74 @@ def main():
             line["oracle_fixture_cpu_s"] = fixture.get("cpu_seconds")
         print(json.dumps(line), flush=True)
         if order == "nd":
-            print(json.dumps(nd_factor_line(A, B, args, by_value, line["wall_ms"], x)), flush=True)
+            print(json.dumps(nd_factor_line(A, B, args, by_value, line["wall_ms"], x, (n, rp, ci, v))), flush=True)
 
 
-def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused):
+def nd_factor_ops(f, A, B, reps, pattern):
+    """What the kept factor does beyond solve and export, host wall ms around
+    synchronous calls. refactor_ms: NdFactor.refactor alternating two value
+    sets of the pattern (A2 = D A D on a handle of its own, whose pattern the
+    factor compares with its copy; A on the handle the plan came from);
+    logdet_ms; solve_dev_ms: device.nd_factor_solve, one column, b and x
+    resident in HBM; solve_L_ms / solve_Lt_ms: the forward / backward pass
+    alone through the host-buffer call. f ends holding A's factor again."""
+    import torch
+
+    from basic_sparse_matrix_amd import device
+
+    n, rp, ci, v = pattern
+    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
+    d = 1.0 + np.random.default_rng(11).random(n)
+    A2 = Csr.from_csr_arrays((n, n), rp, ci, (d[rows] * v * d[ci.astype(np.int64)]).astype(v.dtype))
+    A2._device()
+    f.refactor(A2)  # warm-up: the handle's upload, the temporaries
+    f.refactor(A)
+    t_re, st_re = [], []
+    for i in range(2 * max(reps, 2)):
+        t0 = time.perf_counter()
+        f.refactor(A if i % 2 else A2)
+        t_re.append(time.perf_counter() - t0)
+        st_re.append(_lib.stage_times())
+
+    def timed(fn, count):
+        fn()  # warm-up
+        ts = []
+        for _ in range(count):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    count = max(5 * reps, 10)
+    t_ld = timed(f.logdet, count)
+    logdet = f.logdet()
+    bd = torch.tensor(np.ascontiguousarray(B.get_col(0)), device="cuda")
+    xd = torch.empty_like(bd)
+    t_dev = timed(lambda: device.nd_factor_solve(f, bd, out=xd), count)
+    t_l = timed(lambda: f.solve(B, system="L"), count)
+    t_lt = timed(lambda: f.solve(B, system="Lt"), count)
+    x_host = np.asarray(f.solve(B).get_col(0))
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    mm = lambda t: [round(1e3 * min(t), 3), round(1e3 * max(t), 3)]  # noqa: E731
+    return {
+        "refactor_ms": med(t_re), "refactor_ms_min_max": mm(t_re), "refactor_calls": len(t_re),
+        "refactor_stages_ms": {k: round(float(np.mean([s[k] for s in st_re])), 3) for k in st_re[-1]},
+        "logdet_ms": med(t_ld), "logdet": logdet,
+        "solve_dev_ms": med(t_dev), "solve_dev_ms_min_max": mm(t_dev),
+        "solve_dev_bits_equal_host_solve": bool(np.array_equal(xd.cpu().numpy(), x_host)),
+        "solve_L_ms": med(t_l), "solve_Lt_ms": med(t_lt),
+    }
+
+
+def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused, pattern):
     """The kept factor (cholesky_nd / NdFactor) on the same system: host wall
     clock around synchronous calls. factor_ms: cholesky_nd on the warm handle
     (plan cached; the factor's own fronts allocated inside the clock);
     solve_only_ms: the median of repeated NdFactor.solve calls on ONE factor
     (host b in, host x out, as solve()); export_ms: bsm_nd_factor_export of
     both L and L^T as device handles (no download). The yardsticks from the
-    same process: the fused solve by value and on the same handle."""
+    same process: the fused solve by value and on the same handle. Then
+    nd_factor_ops' figures."""
     import ctypes
 
     from basic_sparse_matrix_amd import cholesky_nd
@@ -350,6 +407,7 @@ def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused):
         "metric": "C5 nd factor object: factor once, solve many, export L (host wall ms around synchronous calls)",
         "config": {"order": "nd", "dtype": args.dtype, "g": args.g, "rhs": 1},
         "factor_ms": med(t_factor),
+        "factor_ms_min_max": [round(1e3 * min(t_factor), 3), round(1e3 * max(t_factor), 3)],
         "solve_only_ms": med(t_solve),
         "solve_only_ms_min_max": [round(1e3 * min(t_solve), 3), round(1e3 * max(t_solve), 3)],
         "solve_only_calls": len(t_solve),
@@ -363,6 +421,7 @@ def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused):
         "rel_dev_vs_fused_solve": float(np.linalg.norm(np.asarray(xf, np.float64) - np.asarray(x_fused, np.float64))
                                         / np.linalg.norm(np.asarray(x_fused, np.float64))),
     }
+    out.update(nd_factor_ops(f, A, B, reps, pattern))
     f.close()
     return out
 
