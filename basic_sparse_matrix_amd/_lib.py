@@ -115,6 +115,8 @@ SIGNATURES = [
     ("bsm_nd_factor_logdet", _int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     ("bsm_nd_factor_solve_system", _int, [_vp, _int, _u64, _u64, _pp, _pp]),
     ("bsm_dev_nd_factor_solve", _int, [_vp, _int, _u64, _vp, _vp, _vp]),
+    ("bsm_nd_factor_selinv", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    ("bsm_dev_nd_factor_inv_diag", _int, [_vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),

@@ -382,4 +382,10 @@ int nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a, hipStream_t s);
 int nd_factor_logdet(const bsm_nd_factor* f, double* logdet, hipStream_t s);
 int nd_factor_perm(const bsm_nd_factor* f, int64_t* perm, hipStream_t s);
 int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipStream_t s);
+// Z = A^-1 on the pattern of L + L^T: the diagonal (A's order) into diag_dev
+// (or null), Z[rows[e]][cols[e]] (A's order, indices < n, uint64 on the
+// device) into vals_dev for e < nq. *n_miss pairs lie outside the pattern,
+// the first of them at *first_miss (their vals are 0).
+int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const uint64_t* rows_dev,
+                     const uint64_t* cols_dev, void* vals_dev, uint64_t* n_miss, uint64_t* first_miss, hipStream_t s);
 }  // namespace bsm

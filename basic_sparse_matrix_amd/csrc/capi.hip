@@ -1132,6 +1132,52 @@ int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, cons
     return nd_factor_solve(f, system, k, f->n, b, x, static_cast<hipStream_t>(stream));
 }
 
+int bsm_nd_factor_selinv(const bsm_nd_factor* f, void* diag, uint64_t nq, const uint64_t* rows,
+                         const uint64_t* cols, void* vals) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(diag || nq > 0, BSM_ERR_INVALID, "null argument: neither diag nor pairs asked for");
+    BSM_REQUIRE(nq == 0 || (rows && cols && vals), BSM_ERR_INVALID, "null argument");
+    for (uint64_t e = 0; e < nq; ++e)
+        BSM_REQUIRE(rows[e] < f->n && cols[e] < f->n, BSM_ERR_OUT_OF_BOUNDS,
+                    "nd factor selinv: pair %llu is (%llu, %llu), the matrix is %llu x %llu", (unsigned long long)e,
+                    (unsigned long long)rows[e], (unsigned long long)cols[e], (unsigned long long)f->n,
+                    (unsigned long long)f->n);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    const size_t es = dtype_size(f->dtype);
+    DBuf dd, dr, dc, dvl;
+    if (diag) BSM_TRY(dd.alloc((size_t)f->n * es, s));
+    if (nq > 0) {
+        BSM_TRY(dr.alloc((size_t)nq * 8, s));
+        BSM_TRY(dc.alloc((size_t)nq * 8, s));
+        BSM_TRY(dvl.alloc((size_t)nq * es, s));
+        BSM_TRY(h2d_staged(dr.p, rows, (size_t)nq * 8, s));
+        BSM_TRY(h2d_staged(dc.p, cols, (size_t)nq * 8, s));
+    }
+    uint64_t n_miss = 0, first = 0;
+    BSM_TRY(nd_factor_selinv(f, diag ? dd.p : nullptr, nq, dr.as<uint64_t>(), dc.as<uint64_t>(), dvl.p, &n_miss,
+                             &first, s));
+    BSM_REQUIRE(n_miss == 0, BSM_ERR_INVALID,
+                "nd factor selinv: %llu of %llu pairs lie outside the pattern of L + L^T; the first is pair %llu, "
+                "(%llu, %llu)",
+                (unsigned long long)n_miss, (unsigned long long)nq, (unsigned long long)first,
+                (unsigned long long)rows[first], (unsigned long long)cols[first]);
+    if (diag && f->n > 0) BSM_TRY(d2h_staged(diag, dd.p, (size_t)f->n * es, s));
+    if (nq > 0) BSM_TRY(d2h_staged(vals, dvl.p, (size_t)nq * es, s));
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(f->n == 0 || diag, BSM_ERR_INVALID, "null argument");
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    uint64_t n_miss = 0, first = 0;
+    return nd_factor_selinv(f, diag, 0, nullptr, nullptr, nullptr, &n_miss, &first, static_cast<hipStream_t>(stream));
+}
+
 int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
     std::lock_guard<std::mutex> lk(f->mu);

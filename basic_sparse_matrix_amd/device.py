@@ -196,6 +196,27 @@ def nd_factor_solve(factor, b: torch.Tensor, out: torch.Tensor | None = None, *,
     return out
 
 
+def nd_factor_inv_diag(factor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
+    """``diag(A^-1)`` of a kept factor (``solver.NdFactor.inv_diag``) into a
+    device tensor (``bsm_dev_nd_factor_inv_diag``): ``(n,)``, contiguous, of
+    the factor's dtype, on its device; ``out`` defaults to a new tensor. Runs
+    on ``stream`` and returns after it has drained; the same kernels and bits
+    as ``NdFactor.inv_diag()``."""
+    from .sparse import _raise_for
+
+    h = factor._h()
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    out = torch.empty((factor.n,), dtype=want, device="cuda") if out is None else out
+    if out.dtype != want:
+        raise TypeError(f"nd_factor_inv_diag: out is {out.dtype}, the factor is {factor.dtype}")
+    if not out.is_cuda:
+        raise ValueError("nd_factor_inv_diag: out is not on the device")
+    if out.dim() != 1 or out.shape[0] != factor.n or not out.is_contiguous():
+        raise ValueError(f"nd_factor_inv_diag: out must be contiguous, ({factor.n},), got {tuple(out.shape)}")
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_inv_diag(h, _p(out), _stream(stream)))
+    return out
+
+
 class Compactor:
     """Dense Y -> output Csr (the zero-dropping insert of sparse.rs:229) with
     preallocated worst-case buffers, so a timed step allocates nothing."""

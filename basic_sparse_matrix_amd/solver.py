@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .dense import Dense
 from .sparse import Csr, _raise_for
-from .util import Panic
+from .util import MatErr, MatErrKind, Panic
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 
@@ -100,7 +100,9 @@ class NdFactor:
     device (``bsm_nd_factor``): factor once with :func:`cholesky_nd`, then
     ``solve`` as often as wanted (``A``, ``L`` or ``L^T``), read ``L`` or
     ``logdet()`` out, and ``refactor`` new values of the same pattern in
-    place (``device.nd_factor_solve`` solves on device tensors). The handle owns its
+    place (``device.nd_factor_solve`` solves on device tensors), and read the
+    selected inverse (``inv_diag()``, ``inv_entries()``, ``inv_on()``:
+    ``A^-1`` on the pattern of ``L + L^T``). The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
@@ -168,6 +170,64 @@ class NdFactor:
         v = ctypes.c_double()
         _raise_for(_lib.require_device().bsm_nd_factor_logdet(h, ctypes.byref(v)))
         return v.value
+
+    def _selinv(self, want_diag: bool, rows, cols):
+        """``bsm_nd_factor_selinv``: (diag or None, vals or None)."""
+        h = self._h()
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        c = np.ascontiguousarray(cols, dtype=np.uint64)
+        diag = np.zeros(self.n, dtype=self.dtype) if want_diag else None
+        nq = r.shape[0]
+        vals = np.zeros(nq, dtype=self.dtype)
+        if (want_diag and self.n) or nq:
+            lib = _lib.require_device()
+            _raise_for(lib.bsm_nd_factor_selinv(h, _lib.ptr(diag) if want_diag else None, nq, _lib.ptr(r),
+                                                _lib.ptr(c), _lib.ptr(vals)))
+        return diag, vals
+
+    def inv_diag(self) -> np.ndarray:
+        """``diag(A^-1)`` in A's order (the marginal variances of a Gaussian
+        with precision ``A``), ``n`` values of the factor's dtype: the
+        selected inverse by the Takahashi recursion over the fronts
+        (``bsm_nd_factor_selinv``), a few times the factor's flops instead of
+        ``n`` solves. Allocates a second set of fronts for the call. Every
+        sum has a fixed order: the same bits on every call."""
+        self._h()
+        return self._selinv(True, (), ())[0]
+
+    def inv_entries(self, rows, cols) -> np.ndarray:
+        """``(A^-1)[rows[e], cols[e]]`` for pairs on the pattern of ``L + L^T``
+        (A's order, either triangle: ``(i, j)`` and ``(j, i)`` give the same
+        bits). ``rows`` and ``cols`` are 1-D integer array-likes of equal
+        length. An index ``>= n`` raises ``MatErr(OutOfBounds)``; a pair
+        outside the pattern raises the error for ``BSM_ERR_INVALID`` naming
+        how many pairs and the first one."""
+        self._h()
+        r, c = np.asarray(rows), np.asarray(cols)
+        if r.ndim != 1 or c.ndim != 1 or r.shape != c.shape:
+            raise ValueError(f"NdFactor.inv_entries: rows and cols must be 1-D of equal length, got "
+                             f"{r.shape} and {c.shape}")
+        for name, x in (("rows", r), ("cols", c)):
+            if x.size and not np.issubdtype(x.dtype, np.integer):
+                raise TypeError(f"NdFactor.inv_entries: {name} must be integers, got {x.dtype}")
+            if x.size and int(x.min()) < 0:
+                raise ValueError(f"NdFactor.inv_entries: {name} has a negative index")
+        return self._selinv(False, r, c)[1]
+
+    def inv_on(self, a: Csr) -> Csr:
+        """``A^-1`` on ``a``'s own stored pattern: a ``Csr`` with ``a``'s
+        ``row_index`` / ``col_index`` and the values ``(A^-1)[i, j]``. Every
+        stored entry of the factored matrix lies in the fronts, so this never
+        raises for it. Zeros are KEPT: the pattern is ``a``'s, not
+        ``Csr::insert``'s zero-dropping rule. ``a`` of another shape raises
+        ``MatErr(IncorrectDimensions)``."""
+        self._h()
+        if a.dims.rows != self.n or a.dims.cols != self.n:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        rp, ci, _ = a._csr_arrays()
+        rows = np.repeat(np.arange(self.n, dtype=np.uint64), np.diff(rp.astype(np.int64)))
+        vals = self._selinv(False, rows, ci)[1]
+        return Csr.from_csr_arrays((self.n, self.n), rp, ci, vals, dtype=self.dtype)
 
     @property
     def perm(self) -> np.ndarray:

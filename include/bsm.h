@@ -290,6 +290,30 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    word is read back: synchronous for that stream. The same kernels, hence
  *    the same bits, as the host call. A null pointer with n k > 0 ->
  *    BSM_ERR_INVALID.
+ *  - bsm_nd_factor_selinv: the selected inverse, Z = A^-1 on the pattern of
+ *    L + L^T (the marginal variances and neighbour covariances of a Gaussian
+ *    with precision A), by the Takahashi recursion over the factor's fronts:
+ *    a few times the factor's own flops instead of n solves. diag: n values,
+ *    diag[i] = Z[i][i] in A's order, or NULL. vals[e] = Z[rows[e]][cols[e]]
+ *    for e < nq, indices in A's order, either triangle ((i, j) and (j, i)
+ *    give the same bits); rows / cols / vals may be NULL when nq == 0. Host
+ *    buffers, diag and vals of the factor's dtype. Errors: a null f,
+ *    diag == NULL with nq == 0, or a null among rows / cols / vals with
+ *    nq > 0 -> BSM_ERR_INVALID ("null ..."), before any device is asked for;
+ *    an index >= n -> BSM_ERR_OUT_OF_BOUNDS; a pair outside the pattern of
+ *    L + L^T (every stored entry of A is inside it) -> BSM_ERR_INVALID naming
+ *    how many pairs and the first one; a handle without values (a failed
+ *    refactor) -> BSM_ERR_INVALID as for the solves. On every error diag and
+ *    vals are untouched. The call allocates Z (a second set of fronts: 8
+ *    bytes x the factor's front elements, 5.98 GB at C5 in f64) and a 64-wide
+ *    panel per front, and frees them before it returns; they are not part of
+ *    bsm_nd_factor_info's *bytes nor of the plan cache's budget. The factor is
+ *    only read. Every sum has a fixed order: the same bits on every call.
+ *    Synchronous; other calls on the handle run before or after it.
+ *  - bsm_dev_nd_factor_inv_diag: the diagonal alone into HBM on the factor's
+ *    device (n values of its dtype), on `stream`; returns after the stream has
+ *    drained. The same kernels and bits as bsm_nd_factor_selinv's diag. A null
+ *    f, or a null diag with n > 0 -> BSM_ERR_INVALID.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -307,6 +331,9 @@ int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, u
                                const void* const* b_cols, void* const* x_cols);
 int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, const void* b, void* x,
                             void* stream);
+int bsm_nd_factor_selinv(const bsm_nd_factor* f, void* diag, uint64_t nq, const uint64_t* rows,
+                         const uint64_t* cols, void* vals);
+int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

@@ -811,6 +811,24 @@ public:
         return out;
     }
 
+    /// diag(A^-1) in A's order (bsm_nd_factor_selinv): the selected inverse by
+    /// the Takahashi recursion over the fronts; the same bits on every call.
+    std::vector<T> inv_diag() const {
+        std::vector<T> d(n_);
+        if (n_ > 0) detail::check(bsm_nd_factor_selinv(f_.get(), d.data(), 0, nullptr, nullptr, nullptr));
+        return d;
+    }
+
+    /// (A^-1)[rows[e]][cols[e]] for pairs on the pattern of L + L^T (A's order,
+    /// either triangle). An index >= n or a pair outside the pattern throws.
+    std::vector<T> inv_entries(const std::vector<uint64_t>& rows, const std::vector<uint64_t>& cols) const {
+        if (rows.size() != cols.size()) throw std::invalid_argument("NdFactor::inv_entries: rows and cols differ in length");
+        std::vector<T> v(rows.size());
+        if (!rows.empty())
+            detail::check(bsm_nd_factor_selinv(f_.get(), nullptr, rows.size(), rows.data(), cols.data(), v.data()));
+        return v;
+    }
+
     /// perm[new] = old.
     std::vector<int64_t> perm() const {
         std::vector<int64_t> p(n_);

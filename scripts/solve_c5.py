@@ -163,6 +163,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-grid-rows", type=int, default=25,
                     help="CPU baseline: leading grid rows of the system timed on this host (x N/R)")
+    ap.add_argument("--kernel-stats", default=None,
+                    help="a rocprofv3 kernel-stats CSV of an earlier run of this command: the nd factor line then "
+                         "carries the selected inverse's device time per kernel and call (selinv_kernels_ms)")
     args = ap.parse_args()
     dt = np.float64 if args.dtype == "f64" else np.float32
     g = args.g
@@ -304,14 +307,42 @@ def main():
             print(json.dumps(nd_factor_line(A, B, args, by_value, line["wall_ms"], x, (n, rp, ci, v))), flush=True)
 
 
-def nd_factor_ops(f, A, B, reps, pattern):
+def selinv_kernel_split(path, dtype):
+    """{nd_selinv_* kernel: device ms per selected inverse} from a rocprofv3 kernel-stats CSV (one
+    nd_selinv_diag_out launch per inv_diag call)."""
+    import csv
+
+    tot, calls = {}, {}
+    with open(path) as fh:
+        for row in csv.DictReader(fh):
+            name = row["Name"]
+            if "nd_selinv_" not in name or f"<{dtype}>" not in name:
+                continue
+            short = name[name.index("nd_selinv_"):].split("<")[0]
+            tot[short] = tot.get(short, 0) + int(row["TotalDurationNs"])
+            calls[short] = calls.get(short, 0) + int(row["Calls"])
+    n = calls.get("nd_selinv_diag_out", 0)
+    if n == 0:
+        return None
+    out = {k: round(v * 1e-6 / n, 4) for k, v in sorted(tot.items())}
+    out["launches_per_call"] = round(sum(calls.values()) / n, 1)
+    out["calls"] = n
+    return out
+
+
+def nd_factor_ops(f, A, B, reps, pattern, kernel_stats=None):
     """What the kept factor does beyond solve and export, host wall ms around
     synchronous calls. refactor_ms: NdFactor.refactor alternating two value
     sets of the pattern (A2 = D A D on a handle of its own, whose pattern the
     factor compares with its copy; A on the handle the plan came from);
     logdet_ms; solve_dev_ms: device.nd_factor_solve, one column, b and x
     resident in HBM; solve_L_ms / solve_Lt_ms: the forward / backward pass
-    alone through the host-buffer call. f ends holding A's factor again."""
+    alone through the host-buffer call; selinv_ms: NdFactor.inv_diag (host
+    out), selinv_dev_ms: device.nd_factor_inv_diag into a resident tensor,
+    selinv_alloc_ms: the stage before the first kernel (Z and the panels
+    allocated; they are freed again inside the call's wall time),
+    selinv_device_ms: the levels' kernels between their stage marks. f ends
+    holding A's factor again."""
     import torch
 
     from basic_sparse_matrix_amd import device
@@ -348,6 +379,17 @@ def nd_factor_ops(f, A, B, reps, pattern):
     t_l = timed(lambda: f.solve(B, system="L"), count)
     t_lt = timed(lambda: f.solve(B, system="Lt"), count)
     x_host = np.asarray(f.solve(B).get_col(0))
+    st_si = []
+
+    def inv_diag_staged():
+        f.inv_diag()
+        st_si.append(_lib.stage_times())
+
+    n_si = max(reps, 3)
+    t_si = timed(inv_diag_staged, n_si)
+    dd = torch.empty(n, dtype=bd.dtype, device="cuda")
+    t_sid = timed(lambda: device.nd_factor_inv_diag(f, dd), n_si)
+    diag = f.inv_diag()
     med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
     mm = lambda t: [round(1e3 * min(t), 3), round(1e3 * max(t), 3)]  # noqa: E731
     return {
@@ -357,6 +399,14 @@ def nd_factor_ops(f, A, B, reps, pattern):
         "solve_dev_ms": med(t_dev), "solve_dev_ms_min_max": mm(t_dev),
         "solve_dev_bits_equal_host_solve": bool(np.array_equal(xd.cpu().numpy(), x_host)),
         "solve_L_ms": med(t_l), "solve_Lt_ms": med(t_lt),
+        "selinv_ms": med(t_si), "selinv_ms_min_max": mm(t_si), "selinv_calls": len(t_si),
+        "selinv_dev_ms": med(t_sid), "selinv_dev_ms_min_max": mm(t_sid),
+        "selinv_alloc_ms": round(float(np.median([s.get("nd_selinv_alloc", 0.0) for s in st_si[1:]])), 3),
+        "selinv_device_ms": round(float(np.median([s.get("nd_selinv", 0.0) for s in st_si[1:]])), 3),
+        "selinv_dev_bits_equal_host": bool(np.array_equal(dd.cpu().numpy(), diag)),
+        "selinv_diag_min_max": [float(diag.min()), float(diag.max())],
+        "selinv_kernels_ms": selinv_kernel_split(kernel_stats, "double" if v.dtype == np.float64 else "float")
+        if kernel_stats else None,
     }
 
 
@@ -421,7 +471,7 @@ def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused, pattern):
         "rel_dev_vs_fused_solve": float(np.linalg.norm(np.asarray(xf, np.float64) - np.asarray(x_fused, np.float64))
                                         / np.linalg.norm(np.asarray(x_fused, np.float64))),
     }
-    out.update(nd_factor_ops(f, A, B, reps, pattern))
+    out.update(nd_factor_ops(f, A, B, reps, pattern, args.kernel_stats))
     f.close()
     return out
 
