@@ -139,6 +139,8 @@ SIGNATURES = [
     ("bsm_tiled_info", _int, [_vp, _u64p, _u64p, _u64p]),
     ("bsm_tiled_destroy", None, [_vp]),
     ("bsm_csr_tiled", _int, [_vp, ctypes.POINTER(_int)]),
+    ("bsm_xfer_counters", _int, [_u64p]),
+    ("bsm_xfer_counters_reset", None, []),
     ("bsm_dev_compact", _int, [_int, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     # multi-GPU (row blocks + RCCL all-gather)
     ("bsm_multi_create", _int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_vp)]),

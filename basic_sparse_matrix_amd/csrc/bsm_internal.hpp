@@ -301,6 +301,7 @@ bool host_registered(const void* p);
 int d2h_csr_direct(const int64_t* rp, const int32_t* col, const void* vals, uint64_t rows, uint64_t nnz, size_t es,
                    uint64_t* row_ptr, uint64_t* col_idx, void* vals_out, hipStream_t s);
 int d2h_cols_widen(uint64_t* dst, const int32_t* src, uint64_t n, hipStream_t s);
+void xfer_count_small_pinned();  // bsm_xfer_counters: a download through the one pinned buffer
 
 // kernels (kernels_*.hip), all async on stream s
 uint64_t scan_workspace_bytes(uint64_t n);

@@ -857,6 +857,7 @@ int bsm_csr_download(const bsm_csr* m, uint64_t* row_ptr, uint64_t* col_idx, voi
         return BSM_OK;
     }
     // small: three copies into one pinned buffer, one sync
+    xfer_count_small_pinned();
     int64_t* rp64 = reinterpret_cast<int64_t*>(pin);
     int32_t* c32 = reinterpret_cast<int32_t*>(pin + rp_b);
     char* vdst = pin + rp_b + col_b;

@@ -17,10 +17,10 @@
 #include <cstring>
 #include <thread>
 
-#include <sys/mman.h>
 #include <vector>
 
 #include "bsm_internal.hpp"
+#include "xfer_host.hpp"
 
 namespace bsm {
 namespace {
@@ -32,26 +32,16 @@ size_t env_size(const char* name, size_t dflt) {
     return e ? (size_t)strtoull(e, nullptr, 10) : dflt;
 }
 
-// memcpy split over a few threads (one host thread copies ~10 GB/s, PCIe
-// moves ~50 GB/s)
-void par_memcpy(void* dst, const void* src, size_t n) {
+// BSM_COPY_THREADS (default 4, 1..16): threads of one chunk's host copy
+void copy_chunk(void* dst, const void* src, size_t n) {
     static const int threads = (int)std::clamp<size_t>(env_size("BSM_COPY_THREADS", 4), 1, 16);
-    const int t = n >= (4ull << 20) ? threads : 1;
-    if (t == 1) {
-        std::memcpy(dst, src, n);
-        return;
-    }
-    const size_t part = (n / t + 4095) & ~size_t(4095);
-    std::thread th[16];
-    int used = 0;
-    for (int i = 1; i < t; ++i) {
-        const size_t off = part * i;
-        if (off >= n) break;
-        th[used++] = std::thread([=] { std::memcpy(static_cast<char*>(dst) + off, static_cast<const char*>(src) + off,
-                                                   std::min(part, n - off)); });
-    }
-    std::memcpy(dst, src, std::min(part, n));
-    for (int i = 0; i < used; ++i) th[i].join();
+    bsm::par_memcpy(dst, src, n, threads);
+}
+
+// BSM_TOUCH_THREADS (default 8, 0..32): threads that fault result pages in
+int touch_threads() {
+    static const int threads = (int)std::clamp<size_t>(env_size("BSM_TOUCH_THREADS", 8), 0, 32);
+    return threads;
 }
 
 // two pinned chunk buffers and their events, per thread
@@ -135,57 +125,6 @@ __global__ __launch_bounds__(256) void widen_i32_u64(const int32_t* __restrict__
 
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
-// Fault in [p, p + bytes) chunk by chunk from BSM_TOUCH_THREADS threads
-// (default 8): a write per 4 KiB page; wait(i) returns once chunk i is in.
-class Prefault {
-public:
-    Prefault(char* p, size_t bytes, size_t chunk) : p_(p), bytes_(bytes), chunk_(chunk) {
-        static const int threads = (int)std::clamp<size_t>(env_size("BSM_TOUCH_THREADS", 8), 0, 32);
-        n_ = (bytes + chunk - 1) / chunk;
-        if (threads == 0 || bytes < (8ull << 20)) {
-            n_ = 0;  // small: the DMA takes its own faults
-            return;
-        }
-        // transparent huge pages for the 2 MiB-aligned interior (advice only;
-        // the box runs THP in madvise mode): 520 MB faults in 3.8 ms on 8
-        // threads with it, 30-40 ms without (profiles/r03_e_first_touch.log)
-        const uintptr_t a0 = ((uintptr_t)p + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1);
-        const uintptr_t a1 = ((uintptr_t)p + bytes) & ~(uintptr_t)((2u << 20) - 1);
-        if (a1 > a0) (void)madvise((void*)a0, a1 - a0, MADV_HUGEPAGE);
-        ready_.reset(new std::atomic<int>[n_]);
-        for (size_t i = 0; i < n_; ++i) ready_[i].store(0, std::memory_order_relaxed);
-        for (int t = 0; t < threads; ++t)
-            th_.emplace_back([this] {
-                for (;;) {
-                    const size_t i = next_.fetch_add(1, std::memory_order_relaxed);
-                    if (i >= n_ || stop_.load(std::memory_order_relaxed)) return;
-                    char* q = p_ + i * chunk_;
-                    const size_t len = std::min(chunk_, bytes_ - i * chunk_);
-                    for (size_t o = 0; o < len; o += 4096) reinterpret_cast<volatile char*>(q)[o] = 0;
-                    ready_[i].store(1, std::memory_order_release);
-                }
-            });
-    }
-    void wait(size_t i) {
-        if (i >= n_) return;
-        while (!ready_[i].load(std::memory_order_acquire)) std::this_thread::yield();
-    }
-    void finish() {
-        stop_.store(true, std::memory_order_relaxed);
-        for (auto& t : th_) t.join();
-        th_.clear();
-    }
-    ~Prefault() { finish(); }
-
-private:
-    char* p_;
-    size_t bytes_, chunk_, n_ = 0;
-    std::unique_ptr<std::atomic<int>[]> ready_;
-    std::atomic<size_t> next_{0};
-    std::atomic<bool> stop_{false};
-    std::vector<std::thread> th_;
-};
-
 }  // namespace
 
 // Host -> device, synchronous (src may be released when it returns). The
@@ -203,6 +142,7 @@ static int h2d_pipeline(void* dst, const void* src, size_t bytes, hipStream_t s,
             const size_t off = i * C, len = std::min(C, bytes - off);
             void* d = dev_stage ? static_cast<char*>(dev_stage) + (i & 1) * C : static_cast<char*>(dst) + off;
             BSM_HIP_TRY(hipMemcpyAsync(d, static_cast<const char*>(src) + off, len, hipMemcpyHostToDevice, s));
+            xfer_count(XFER_H2D_DIRECT_CHUNKS);
             if (dev_stage) BSM_TRY(post(off, len, d));
         }
         BSM_HIP_TRY(hipStreamSynchronize(s));
@@ -215,9 +155,10 @@ static int h2d_pipeline(void* dst, const void* src, size_t bytes, hipStream_t s,
         const size_t off = i * C, len = std::min(C, bytes - off);
         const int b = (int)(i & 1);
         if (i >= 2) BSM_HIP_TRY(hipEventSynchronize(st.ev[b]));
-        par_memcpy(st.buf[b], static_cast<const char*>(src) + off, len);
+        copy_chunk(st.buf[b], static_cast<const char*>(src) + off, len);
         void* d = dev_stage ? static_cast<char*>(dev_stage) + (size_t)b * C : static_cast<char*>(dst) + off;
         BSM_HIP_TRY(hipMemcpyAsync(d, st.buf[b], len, hipMemcpyHostToDevice, s));
+        xfer_count(XFER_H2D_STAGED_CHUNKS);
         if (dev_stage) BSM_TRY(post(off, len, d));
         BSM_HIP_TRY(hipEventRecord(st.ev[b], s));
     }
@@ -245,7 +186,7 @@ static int d2h_pipeline(void* dst, const void* src, size_t bytes, hipStream_t s,
         const size_t n = (bytes + C - 1) / C;
         static const bool dbg = getenv("BSM_XFER_DEBUG") != nullptr;
         const auto t0 = host_now();
-        Prefault pf(static_cast<char*>(dst), bytes, C);
+        Prefault pf(static_cast<char*>(dst), bytes, C, touch_threads());
         double t_wait = 0, t_dma = 0;
         int rc = BSM_OK;
         for (size_t i = 0; i < n && rc == BSM_OK; ++i) {
@@ -266,6 +207,7 @@ static int d2h_pipeline(void* dst, const void* src, size_t bytes, hipStream_t s,
                 rc = BSM_ERR_HIP;
             }
             t_dma += ms_since(tw);
+            if (rc == BSM_OK) xfer_count(XFER_D2H_DIRECT_CHUNKS);
         }
         pf.finish();
         BSM_TRY(rc);
@@ -278,12 +220,13 @@ static int d2h_pipeline(void* dst, const void* src, size_t bytes, hipStream_t s,
     Stage& st = stage();
     BSM_TRY(st.get(std::min(C, bytes)));
     const size_t n = (bytes + C - 1) / C;
-    Prefault pf(static_cast<char*>(dst), bytes, C);  // fresh result pages, faulted in ahead of the copies
+    Prefault pf(static_cast<char*>(dst), bytes, C, touch_threads());  // fresh result pages, faulted in ahead of the copies
     auto drain = [&](size_t i) -> int {  // chunk i's DMA done -> copy out of its pinned buffer
         const size_t off = i * C, len = std::min(C, bytes - off);
         BSM_HIP_TRY(hipEventSynchronize(st.ev[i & 1]));
         pf.wait(i);
-        par_memcpy(static_cast<char*>(dst) + off, st.buf[i & 1], len);
+        copy_chunk(static_cast<char*>(dst) + off, st.buf[i & 1], len);
+        xfer_count(XFER_D2H_STAGED_CHUNKS);
         return BSM_OK;
     };
     for (size_t i = 0; i < n; ++i) {
@@ -357,6 +300,7 @@ bool host_registered(const void* p) {
 int d2h_csr_direct(const int64_t* rp, const int32_t* col, const void* vals, uint64_t rows, uint64_t nnz, size_t es,
                    uint64_t* row_ptr, uint64_t* col_idx, void* vals_out, hipStream_t s) {
     DBuf wide;
+    xfer_count(XFER_D2H_CSR_DIRECT_CALLS);
     if (col_idx && nnz) {
         BSM_TRY(wide.alloc(nnz * 8, s));
         widen_i32_u64<<<blocks(nnz), 256, 0, s>>>(col, wide.as<uint64_t>(), nnz);
@@ -382,4 +326,17 @@ int d2h_cols_widen(uint64_t* dst, const int32_t* src, uint64_t n, hipStream_t s)
     });
 }
 
+void xfer_count_small_pinned() { xfer_count(XFER_D2H_SMALL_PINNED_CALLS); }
+
 }  // namespace bsm
+
+extern "C" int bsm_xfer_counters(uint64_t out[8]) {
+    static_assert(bsm::XFER_COUNTERS == 8, "bsm_xfer_counters reports eight counters");
+    BSM_REQUIRE(out, BSM_ERR_INVALID, "null argument");
+    for (int i = 0; i < 8; ++i) out[i] = bsm::g_xfer_counters[i].load(std::memory_order_relaxed);
+    return BSM_OK;
+}
+
+extern "C" void bsm_xfer_counters_reset(void) {
+    for (auto& c : bsm::g_xfer_counters) c.store(0, std::memory_order_relaxed);
+}

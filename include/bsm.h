@@ -430,6 +430,15 @@ int bsm_tiled_info(const bsm_tiled* t, uint64_t* bytes, uint64_t* slots, uint64_
 /* Whether bsm_csr_mul_dense has built (and uses) the tiled copy for this
  * handle; diagnostic. */
 int bsm_csr_tiled(const bsm_csr* m, int* in_use);
+/* Which route the host transfers of this process took so far; diagnostic.
+ * out[0..7]: host-to-device chunks sent direct (pageable DMA) / staged
+ * (pinned pipeline), device-to-host chunks direct / staged, result chunks
+ * faulted in ahead of the data by host threads, chunk copies that used more
+ * than one host thread, bsm_csr_download calls that wrote page-locked
+ * destinations directly, bsm_csr_download calls served by the one small
+ * pinned buffer. Relaxed process-wide counts; _reset zeroes them. */
+int bsm_xfer_counters(uint64_t out[8]);
+void bsm_xfer_counters_reset(void);
 void bsm_tiled_destroy(bsm_tiled* t);
 /* Compaction of a dense result into the reference's output Csr (insert's
  * zero skip, sparse.rs:229): out_row_ptr (rows+1), out_col/out_vals with
