@@ -136,7 +136,9 @@ SIGNATURES = [
     ("bsm_dev_tiled_wanted", _int, [_int, _u64, _u64, _u64, _u64, _u64]),
     ("bsm_dev_tiled_create", _int, [_u64, _u64, _u64, _vp, _vp, _vp, _u64, _int, ctypes.POINTER(_vp), _vp]),
     ("bsm_dev_spmm_tiled", _int, [_vp, _vp, _vp, _vp, _vp]),
-    ("bsm_tiled_info", _int, [_vp, _u64p, _u64p, _u64p]),
+    ("bsm_dev_tiled_half_wanted", _int, [_int, _u64, _u64, _u64, _u64, ctypes.c_uint32]),
+    ("bsm_tiled_info", _int, [_vp, _u64p, _u64p, _u64p, ctypes.POINTER(ctypes.c_uint32),
+                              ctypes.POINTER(ctypes.c_uint32)]),
     ("bsm_tiled_destroy", None, [_vp]),
     ("bsm_csr_tiled", _int, [_vp, ctypes.POINTER(_int)]),
     ("bsm_xfer_counters", _int, [_u64p]),

@@ -199,6 +199,7 @@ struct bsm_tiled {
     uint64_t k = 32;             // right-hand columns the copy serves (32 or 1)
     uint32_t overread = 4;       // chunks of dummy padding past the last task
     uint32_t stage = 4;          // k = 1: chunks per pipeline stage
+    uint32_t passes = 1;         // 2: half-width rows, two sweeps per batch (meta = col << 8 | row >> 1)
     uint64_t rows = 0, n_cols = 0, nnz = 0;
     uint32_t nw = 0, rpw = 0, nb = 0, rw = 0, pshift = 0;
     uint64_t chunks = 0;         // total, without the over-read padding
@@ -334,6 +335,8 @@ int spmm_panelled(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const
                   int32_t* row_nnz, uint64_t panel_cols, const int32_t* seg, hipStream_t s);
 // row-block x column-panel schedule (kernels_tiled.hip)
 bool tiled_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k, uint64_t max_row_len);
+// whether the model picks the two-pass kernel for this shape on `cus` CUs (BSM_TILED_HALF aside)
+bool tiled_half_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k, uint32_t cus);
 // synchronous; the copy must leave `reserve` device bytes free; pt (may be
 // null) receives host times of its phases
 int tiled_create(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const int64_t* rp, const int32_t* col,

@@ -1290,8 +1290,15 @@ int bsm_dev_spmm_tiled(const bsm_tiled* t, const double* x, double* y, int32_t* 
     return tiled_spmm(t, x, y, row_nnz, false, static_cast<hipStream_t>(stream));
 }
 
-int bsm_tiled_info(const bsm_tiled* t, uint64_t* bytes, uint64_t* slots, uint64_t* panel_cols) {
+int bsm_dev_tiled_half_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k, uint32_t cus) {
+    return tiled_half_wanted(dtype, rows, n_cols, nnz, k, cus) ? 1 : 0;
+}
+
+int bsm_tiled_info(const bsm_tiled* t, uint64_t* bytes, uint64_t* slots, uint64_t* panel_cols, uint32_t* passes,
+                   uint32_t* batch_rows) {
     BSM_REQUIRE(t, BSM_ERR_INVALID, "null argument");
+    if (passes) *passes = t->passes;
+    if (batch_rows) *batch_rows = t->rw;
     const uint64_t n = (t->chunks + t->overread) * 64;
     if (bytes) *bytes = n * (t->meta_bytes + (t->dtype == BSM_F32 ? 4 : 8)) + ((uint64_t)t->nw * t->nb + 1) * 8;
     if (slots) *slots = t->chunks * 64;

@@ -34,8 +34,13 @@
 // Lane 16g+q of a chunk handles entry (quad q, group g) at load time; a DPP
 // row broadcast hands entry (u, g) to the 16 lanes of group g, which gather
 // X[col][2q..2q+1] (16 B each, one 256-B row per group).
+//
+// Where the model says it pays (tiled_half_wanted; the C4 shape), f64 on
+// fewer than 2^24 columns runs spmm_tiled_k32_half instead: half-width Y rows,
+// twice as many per wave, every batch swept once per half of k (below).
 #include "bsm_internal.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -52,9 +57,23 @@ constexpr int OVERREAD = 4;      // chunks the pipeline reads past a task's end
 constexpr uint32_t DONE = 0xffffffffu;
 constexpr uint32_t RW_MAX = 155;  // 4 waves x (RW+1) rows x 256 B <= 160 KiB of LDS
 constexpr uint32_t RW_MAX_F32 = 255;  // f32: 128-B rows; the 8-bit row field (dummy row = RW) caps it
-constexpr uint32_t PSHIFT = 12;   // panel = 4096 columns = 1 MiB of X (C4 sweep: 2^10..2^12 flat, 2^13 +12 %, 2^14 +42 %)
+// the two-pass f64 kernel (spmm_tiled_k32_half): 128-B half rows, 9-bit rows
+constexpr uint32_t RW_MAX_HALF = 310;  // 4 waves x (310 + 2 scratch rows) x 128 B = 159,744 B of LDS
+// Gathers one chunk ahead (8 KiB in flight per wave), indices one chunk ahead
+// of them. Deeper is slower here: at C4 two, three and four chunks ahead
+// measured 195, 213 and 221 ms against 176 in the same build (DESIGN.md
+// 4.1f): the waves of an XCD gather a panel together, and a line asked for
+// again while its first fetch is still in flight is fetched again.
+constexpr int H_GATHER_AHEAD = 1;
+constexpr int H_IDX_AHEAD = 2;
+constexpr int H_XRING = H_GATHER_AHEAD + 1, H_IRING = 2 * H_XRING;
+constexpr int PHASES_HALF = H_IRING;   // a multiple of both rings
+constexpr int OVERREAD_HALF = H_IDX_AHEAD;
+constexpr uint32_t PSHIFT = 12;  // panel = 4096 columns = 1 MiB of X (C4 sweep: 2^10..2^12 flat, 2^13 +12 %, 2^14 +42 %)
 constexpr uint32_t PACE_PCT = 3;  // chunk budget per panel over the task's mean (padding ~ this; C4: 2 % +19 %, 6 % +2 %)
 
+// two-pass kernel: the even scratch row of a batch of rw rows (the odd one follows it)
+__host__ __device__ constexpr uint32_t half_scratch_row(uint32_t rw) { return (rw + 1) & ~1u; }
 __device__ __forceinline__ uint64_t lanemask_lt(int lane) {
     return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }
@@ -68,7 +87,11 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 // layout builder: one wave per task (gw, b). COUNT pass writes the task's
 // chunk count (a multiple of PHASES); WRITE pass fills its chunks from offs.
 // ---------------------------------------------------------------------------
-template <bool WRITE, int SLOTS, typename V, typename M = uint32_t>
+// HALF (the two-pass k = 32 f64 kernel): even chunk positions hold even rows,
+// odd positions odd rows, each parity class filled by its own greedy selection
+// of up to 32; meta = col << 8 | row >> 1 (the row's low bit is the
+// position's); two scratch rows, one per parity, above the batch's rows.
+template <bool WRITE, int SLOTS, typename V, typename M = uint32_t, bool HALF = false>
 __global__ __launch_bounds__(256) void tiled_layout(uint64_t rows, uint64_t n_cols, double pace, uint32_t rbits,
                                                     uint32_t pad, const int64_t* __restrict__ rp,
                                                     const int32_t* __restrict__ col,
@@ -106,6 +129,7 @@ __global__ __launch_bounds__(256) void tiled_layout(uint64_t rows, uint64_t n_co
     const double inv_r = t1 > t0 ? (double)CHUNK * np / ((double)(t1 - t0) * pace) : 1e30;
     int64_t c = WRITE ? offs[task] : 0;
     int64_t n = 0;
+    const M dummy = HALF ? (M)(half_scratch_row(rw) >> 1) : (M)rw;
     for (;;) {
         bool sel[SLOTS];
         int pos[SLOTS];
@@ -114,33 +138,43 @@ __global__ __launch_bounds__(256) void tiled_layout(uint64_t rows, uint64_t n_co
             sel[j] = false;
             pos[j] = 0;
         }
-        int taken = 0;
+        constexpr int NCLS = HALF ? 2 : 1;   // parity classes (a row's parity is its lane's)
+        constexpr int CAP = CHUNK / NCLS;    // positions per class
+        int taken[NCLS];
         const double pm = (double)n * inv_r;
         const uint32_t pmax = pm >= 4.0e9 ? DONE - 1 : (uint32_t)pm;
-        bool done = false;
-        while (taken < CHUNK) {  // the lowest panels first, ties by row
-            uint32_t m = DONE;
+        bool done = true;
 #pragma unroll
-            for (int j = 0; j < SLOTS; ++j) m = min(m, sel[j] ? DONE : h[j]);
-            m = wave_min_u32(m);
-            if (m == DONE) {
-                done = taken == 0;
-                break;
-            }
-            if (m > pmax) break;  // ahead of the pace: the rest of the chunk is padding
-            int before = 0;  // candidates in the slots before j (slot order = row order)
+        for (int cls = 0; cls < NCLS; ++cls) {
+            const bool mine = !HALF || (lane & 1) == cls;
+            int tk = 0;
+            bool fin = false;
+            while (tk < CAP) {  // the lowest panels first, ties by row
+                uint32_t m = DONE;
 #pragma unroll
-            for (int j = 0; j < SLOTS; ++j) {
-                const bool cand = !sel[j] && h[j] == m;
-                const uint64_t bal = __ballot(cand);
-                const int rank = before + __popcll(bal & lanemask_lt(lane));
-                if (cand && taken + rank < CHUNK) {
-                    sel[j] = true;
-                    pos[j] = taken + rank;
+                for (int j = 0; j < SLOTS; ++j) m = min(m, (sel[j] || !mine) ? DONE : h[j]);
+                m = wave_min_u32(m);
+                if (m == DONE) {
+                    fin = tk == 0;
+                    break;
                 }
-                before += __popcll(bal);
+                if (m > pmax) break;  // ahead of the pace: the rest of the class is padding
+                int before = 0;  // candidates in the slots before j (slot order = row order)
+#pragma unroll
+                for (int j = 0; j < SLOTS; ++j) {
+                    const bool cand = mine && !sel[j] && h[j] == m;
+                    const uint64_t bal = __ballot(cand);
+                    const int rank = before + __popcll(bal & lanemask_lt(lane));
+                    if (cand && tk + rank < CAP) {
+                        sel[j] = true;
+                        pos[j] = HALF ? 2 * (tk + rank) + cls : tk + rank;
+                    }
+                    before += __popcll(bal);
+                }
+                tk = min(tk + before, CAP);
             }
-            taken = min(taken + before, CHUNK);
+            done = done && fin;
+            taken[cls] = tk;
         }
         if (done) break;
 #pragma unroll
@@ -148,15 +182,17 @@ __global__ __launch_bounds__(256) void tiled_layout(uint64_t rows, uint64_t n_co
             if (sel[j]) {
                 const int64_t e = cur[j];
                 if (WRITE) {
-                    meta[c * CHUNK + pos[j]] = ((M)(uint32_t)col[e] << rbits) | (M)(lane + WAVE * j);
+                    const uint32_t slot = lane + WAVE * j;
+                    meta[c * CHUNK + pos[j]] = ((M)(uint32_t)col[e] << rbits) | (M)(HALF ? slot >> 1 : slot);
                     val[c * CHUNK + pos[j]] = vals[e];
                 }
                 cur[j] = e + 1;
                 h[j] = cur[j] < end[j] ? (uint32_t)col[cur[j]] >> pshift : DONE;
             }
         }
-        if (WRITE && lane >= taken) {  // dummy entries: scratch row rw, X row 0, value 0
-            meta[c * CHUNK + lane] = (M)rw;
+        // dummy entries: scratch row (rw; HALF: the position's parity), X row 0, value 0
+        if (WRITE && (HALF ? (lane >> 1) >= taken[lane & (NCLS - 1)] : lane >= taken[0])) {
+            meta[c * CHUNK + lane] = dummy;
             val[c * CHUNK + lane] = (V)0;
         }
         ++c;
@@ -165,7 +201,7 @@ __global__ __launch_bounds__(256) void tiled_layout(uint64_t rows, uint64_t n_co
     const int64_t padded = (n + pad - 1) / pad * pad;
     if (WRITE) {
         for (int64_t p = n; p < padded; ++p, ++c) {
-            meta[c * CHUNK + lane] = (M)rw;
+            meta[c * CHUNK + lane] = dummy;
             val[c * CHUNK + lane] = (V)0;
         }
     } else if (lane == 0) {
@@ -369,6 +405,132 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // ---------------------------------------------------------------------------
+// k = 32, f64 in two half-row passes (spmm_tiled_k32_half). A wave keeps
+// half-width Y rows (128 B), so an XCD holds twice the rows (4 x 310 per CU)
+// and an X line fetched into L2 serves twice the gathers; every batch is swept
+// twice, once per half of k, at the price of reading its stream twice
+// (tiled_create weighs the two). An 8-lane group gathers one 128-B line of X
+// (16 B per lane, row col, doubles 16h .. 16h + 15), so a gather instruction
+// still moves 1 KiB and a chunk takes 8 of them per pass.
+// Step u of a chunk gives group 2r + s (lanes 16r + 8s .. + 7) the entry that
+// lane 16r + 2u + s loaded: two DPP row shares, one per bank pair (bank_mask
+// 0x3: lanes 0-7 of each row, 0xc: lanes 8-15). The entry's position has
+// parity s, and the layout puts a row of parity s there: the two groups of a
+// 16-lane LDS access always hit complementary halves of the 64 banks. A chunk
+// holds at most one entry of a row, so any map of its entries onto (step,
+// group) keeps each row's storage order: bit-identical to spmm_tiled_k32.
+// ---------------------------------------------------------------------------
+// (the first move of each pair leaves lanes 8-15 undefined: the second writes them)
+template <int U>
+__device__ __forceinline__ uint32_t bm8(uint32_t mi) {
+    const int a = __builtin_amdgcn_mov_dpp((int)mi, 0x150 + 2 * U, 0xf, 0x3, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp(a, (int)mi, 0x150 + 2 * U + 1, 0xf, 0xc, false);
+}
+template <int U>
+__device__ __forceinline__ double bv8(double vi) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(vi), 0x150 + 2 * U, 0xf, 0x3, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(vi), 0x150 + 2 * U, 0xf, 0x3, false);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, __double2hiint(vi), 0x150 + 2 * U + 1, 0xf, 0xc, false),
+                            __builtin_amdgcn_update_dpp(lo, __double2loint(vi), 0x150 + 2 * U + 1, 0xf, 0xc, false));
+}
+// Xh = half h of X row 0 (wave-uniform), j16 = this lane's 16 B in a half row.
+// A row of X is 256 B and columns are < 2^24, so the byte offset of a row is
+// the meta word with its row field cleared: it fits 32 bits and costs one
+// VALU instruction beside the load's own base + offset addressing.
+// mb keeps the broadcast meta words for the chunk's sum (its LDS rows).
+template <bool PROBE, int... U>
+__device__ __forceinline__ void gather_half(double2 (&x)[8], uint32_t (&mb)[8], const Idx<double>& c,
+                                            const char* __restrict__ Xh, uint32_t j16, uint32_t xmask,
+                                            std::integer_sequence<int, U...>) {
+    ((mb[U] = bm8<U>(c.mi)), ...);
+    if (PROBE) ((x[U] = *reinterpret_cast<const double2*>(Xh + ((((mb[U] >> 8) & xmask) << 8) | j16))), ...);
+    else ((x[U] = *reinterpret_cast<const double2*>(Xh + ((mb[U] & 0xffffff00u) | j16))), ...);
+}
+// ys = the wave's LDS rows + 8 s + j: LDS row = (meta & 255) << 1 | s, 128 B each
+__device__ __forceinline__ double2* yaddr_half(uint32_t mb, double2* ys) {
+    return reinterpret_cast<double2*>(reinterpret_cast<char*>(ys) + ((mb & 255u) << 8));
+}
+template <int U>
+__device__ __forceinline__ void madd_half(double2& y, const double2& x, const Idx<double>& c) {
+    const double v = bv8<U>(c.vi);
+    y = make_double2(__dadd_rn(y.x, __dmul_rn(v, x.x)), __dadd_rn(y.y, __dmul_rn(v, x.y)));
+}
+template <int... U>
+__device__ __forceinline__ void sum_chunk_half(const double2 (&x)[8], const uint32_t (&mb)[8], const Idx<double>& c,
+                                               double2* ys, std::integer_sequence<int, U...>) {
+    double2 y[8];
+    ((y[U] = *yaddr_half(mb[U], ys)), ...);
+    (madd_half<U>(y[U], x[U], c), ...);
+    ((*yaddr_half(mb[U], ys) = y[U]), ...);
+}
+
+template <bool PROBE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void spmm_tiled_k32_half(
+    uint64_t rows, uint32_t rpw, uint32_t nb, uint32_t rw, const int64_t* __restrict__ offs,
+    const uint32_t* __restrict__ meta, const double* __restrict__ val, const double2* __restrict__ X,
+    double2* __restrict__ Y, int32_t* __restrict__ row_nnz, unsigned* bar, uint32_t xmask, uint32_t spins) {
+    extern __shared__ __align__(16) unsigned char yhalf_raw[];
+    double2* const yhalf = reinterpret_cast<double2*>(yhalf_raw);
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = threadIdx.x / WAVE;
+    const int g = lane >> 3, j = lane & 7;  // 8-lane group, lane in group
+    double2* yw = yhalf + (size_t)wave * (half_scratch_row(rw) + 2) * 8;
+    double2* ys = yw + (g & 1) * 8 + j;
+    const uint64_t gw = (uint64_t)blockIdx.x * (blockDim.x / WAVE) + wave;
+    const uint64_t w0 = gw * rpw;
+    const uint64_t wend = min<uint64_t>(rows, w0 + rpw);
+    const uint32_t waves = gridDim.x * (blockDim.x / WAVE);
+    constexpr auto SEQ = std::make_integer_sequence<int, 8>{};
+    bool sync = bar != nullptr;
+    for (uint32_t st = 0; st < 2 * nb; ++st) {  // step = (batch, half)
+        const uint32_t b = st >> 1, h = st & 1;
+        const uint64_t r0 = w0 + (uint64_t)b * rw;
+        if (r0 >= wend) {  // out of rows: arrive for the steps left and stop
+            if (sync) batch_arrive(bar, 2 * nb - st, lane);
+            break;
+        }
+        if (sync && st > 0) sync = batch_wait(bar, waves * st, lane, spins);
+        const int nr = (int)min<uint64_t>(rw, wend - r0);
+        for (int r = g; r < nr; r += 8) yw[r * 8 + j] = make_double2(0.0, 0.0);
+        const char* Xh = reinterpret_cast<const char*>(X) + 128 * h;
+        const uint32_t j16 = 16 * j;
+        const int64_t c0 = offs[gw * nb + b], c1 = offs[gw * nb + b + 1];
+        if (c1 > c0) {  // (c1 - c0) % PHASES_HALF == 0
+            Idx<double> MI[H_IRING];
+            double2 XS[H_XRING][8];
+            uint32_t MB[H_XRING][8];
+#pragma unroll
+            for (int k = 0; k < H_IDX_AHEAD; ++k) load_idx(MI[k], meta, val, c0 + k, lane);
+#pragma unroll
+            for (int k = 0; k < H_GATHER_AHEAD; ++k) gather_half<PROBE>(XS[k], MB[k], MI[k], Xh, j16, xmask, SEQ);
+            for (int64_t i = c0; i < c1; i += PHASES_HALF) {
+#pragma unroll
+                for (int k = 0; k < PHASES_HALF; ++k) {
+                    load_idx(MI[(k + H_IDX_AHEAD) % H_IRING], meta, val, i + k + H_IDX_AHEAD, lane);
+                    gather_half<PROBE>(XS[(k + H_GATHER_AHEAD) % H_XRING], MB[(k + H_GATHER_AHEAD) % H_XRING],
+                                       MI[(k + H_GATHER_AHEAD) % H_IRING], Xh, j16, xmask, SEQ);
+                    __builtin_amdgcn_sched_barrier(0);  // this phase's loads stay ahead of its sums
+                    sum_chunk_half(XS[k % H_XRING], MB[k % H_XRING], MI[k], ys, SEQ);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        for (int rb = 0; rb < nr; rb += 8) {  // Y half rows; nonzero counts over both halves
+            const int r = rb + g;
+            const bool live = r < nr;
+            const double2 y = live ? yw[r * 8 + j] : make_double2(0.0, 0.0);
+            if (live) Y[(r0 + r) * 16 + 8 * h + j] = y;
+            const uint64_t m0 = __ballot(y.x != 0.0), m1 = __ballot(y.y != 0.0);
+            if (live && j == 0 && row_nnz) {
+                const int n = __popcll((m0 >> (8 * g)) & 0xffull) + __popcll((m1 >> (8 * g)) & 0xffull);
+                row_nnz[r0 + r] = h ? row_nnz[r0 + r] + n : n;  // the same lane wrote the first half
+            }
+        }
+        if (sync) batch_arrive(bar, 1, lane);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // k = 1 (SpMV, C2's shape): the same copy with RW up to 2047 rows per wave (Y
 // is one double per row: 4 waves x 2048 x 8 B of LDS) and meta = col << 11 |
 // row, so an XCD holds ~125k rows and an X panel of 2 MiB (2^18 columns) is
@@ -506,6 +668,19 @@ bool tiled_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint6
     return max_row_len <= 2 * mean + 256;
 }
 
+// The two-pass kernel's rule (k = 32, f64, columns < 2^24). lambda = the Y
+// rows an XCD holds on chip x the matrix density = the gathers one X line
+// serves per L2 fill; the ideal miss fraction is f = (1 - e^-lambda) / lambda.
+// Half-width rows double lambda and read the 12-B stream entry a second time:
+// they pay when the gather misses saved per entry, f(lambda) - f(2 lambda) of
+// 256 B, exceed those 12 B (lambda between about 0.1 and 10.5).
+bool tiled_half_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k, uint32_t cus) {
+    if (dtype != BSM_F64 || k != 32 || n_cols >= (1ull << 24) || rows == 0 || n_cols == 0 || nnz == 0) return false;
+    const double lam = (double)cus / 8.0 * 4.0 * (double)RW_MAX * (double)nnz / ((double)rows * (double)n_cols);
+    auto f = [](double l) { return l < 1e-9 ? 1.0 : -std::expm1(-l) / l; };
+    return f(lam) - f(2.0 * lam) > 12.0 / 256.0;
+}
+
 int tiled_create(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const int64_t* rp, const int32_t* col,
                  const void* vals, uint64_t k, int flags, bsm_tiled** out, hipStream_t s, uint64_t reserve,
                  PlanTimes* pt) {
@@ -541,14 +716,18 @@ int tiled_create(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const 
     const uint32_t nw_env = env_u32("BSM_TILED_WAVES", wpc * (uint32_t)cus);
     const uint32_t nw = nw_env;
     const uint32_t k1_stage = env_u32("BSM_TILED_K1_STAGE", K1_STAGE_DEFAULT) == 8 ? 8u : 4u;
+    // the two-pass kernel: by the model, or as BSM_TILED_HALF=0|1 says (tests, A/B)
+    const bool half_ok = k == 32 && !f32 && !wide;
+    const bool half = half_ok && env_u32("BSM_TILED_HALF", tiled_half_wanted(dtype, rows, n_cols, nnz, k,
+                                                                              (uint32_t)cus)) != 0;
     const uint32_t rw_cap =
-        k == 1 ? K1_RW_MAX : (f32 ? RW_MAX_F32 : RW_MAX);
+        k == 1 ? K1_RW_MAX : (f32 ? RW_MAX_F32 : (half ? RW_MAX_HALF : RW_MAX));
     uint32_t rw_max = env_u32("BSM_TILED_RW", rw_cap);
     rw_max = rw_max < 8u ? 8u : (rw_max > rw_cap ? rw_cap : rw_max);
     const uint32_t pshift = env_u32("BSM_TILED_PSHIFT", k == 1 ? K1_PSHIFT : PSHIFT);
     const double pace = 1.0 + env_u32("BSM_TILED_PACE_PCT", PACE_PCT) / 100.0;
-    const uint32_t pad = k == 1 ? 1u : PHASES;  // k = 1 runs a task's tail chunks unpipelined
-    const uint32_t overread = k == 1 ? 2 * k1_stage : OVERREAD;
+    const uint32_t pad = k == 1 ? 1u : (half ? PHASES_HALF : PHASES);  // k = 1 runs a task's tail chunks unpipelined
+    const uint32_t overread = k == 1 ? 2 * k1_stage : (half ? OVERREAD_HALF : OVERREAD);
     BSM_REQUIRE(nw >= wpc && nw % wpc == 0 && pshift < 32, BSM_ERR_INVALID, "tiled: bad geometry");
     const uint64_t rpw64 = (rows + nw - 1) / nw;
     BSM_REQUIRE(rpw64 < (1ull << 31), BSM_ERR_UNSUPPORTED, "tiled: too many rows per wave");
@@ -568,7 +747,16 @@ int tiled_create(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const 
                 tiled_layout<W, (K1_RW_MAX + 1) / WAVE, V, MT><<<dim3((unsigned)grid), 256, 0, s>>>(
                     rows, n_cols, pace, rbits, pad, rp, col, static_cast<const V*>(vals), nw, rpw, nb, rw, pshift,
                     cnt, of, static_cast<MT*>(me), static_cast<V*>(va));
-            else if (rw_cap > 192)  // f32 batches up to 255 rows: four row slots per lane
+            else if constexpr (std::is_same_v<V, double> && std::is_same_v<MT, uint32_t>) {
+                if (half)  // batches up to 310 rows: five row slots per lane, rows split by parity
+                    tiled_layout<W, 5, V, MT, true><<<dim3((unsigned)grid), 256, 0, s>>>(
+                        rows, n_cols, pace, rbits, pad, rp, col, static_cast<const V*>(vals), nw, rpw, nb, rw,
+                        pshift, cnt, of, static_cast<MT*>(me), static_cast<V*>(va));
+                else
+                    tiled_layout<W, 3, V, MT><<<dim3((unsigned)grid), 256, 0, s>>>(
+                        rows, n_cols, pace, rbits, pad, rp, col, static_cast<const V*>(vals), nw, rpw, nb, rw,
+                        pshift, cnt, of, static_cast<MT*>(me), static_cast<V*>(va));
+            } else if (rw_cap > 192)  // f32 batches up to 255 rows: four row slots per lane
                 tiled_layout<W, 4, V, MT><<<dim3((unsigned)grid), 256, 0, s>>>(
                     rows, n_cols, pace, rbits, pad, rp, col, static_cast<const V*>(vals), nw, rpw, nb, rw, pshift,
                     cnt, of, static_cast<MT*>(me), static_cast<V*>(va));
@@ -639,6 +827,7 @@ int tiled_create(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const 
     t->chunks = (uint64_t)total;
     t->overread = overread;
     t->stage = k1_stage;
+    t->passes = half ? 2u : 1u;
     t->offs = static_cast<int64_t*>(offs.release());
     t->meta_bytes = (uint32_t)mb;
     t->meta = meta.release();
@@ -653,7 +842,7 @@ int tiled_spmm(const bsm_tiled* t, const void* x, void* y, int32_t* row_nnz, boo
     BSM_REQUIRE(!neg_init || t->k == 1, BSM_ERR_INVALID, "tiled: -0 init only for k = 1");
     if (t->rows == 0) return BSM_OK;
     unsigned* bar = nullptr;
-    if (t->bar && t->nb > 1 && env_u32("BSM_TILED_SYNC", 1)) {
+    if (t->bar && t->nb * t->passes > 1 && env_u32("BSM_TILED_SYNC", 1)) {
         BSM_HIP_TRY(hipMemsetAsync(t->bar, 0, 8 * BAR_STRIDE * sizeof(unsigned), s));
         bar = t->bar;
     }
@@ -696,7 +885,14 @@ int tiled_spmm(const bsm_tiled* t, const void* x, void* y, int32_t* row_nnz, boo
         auto kern = xmask != 0xffffffffu ? spmm_tiled_k32<true>
                                          : spmm_tiled_k32<false>;
         static const uint32_t spins = env_u32("BSM_TILED_SPINS", 4000);
-        if (t->meta_bytes == 8)  // 2^24 columns or more
+        if (t->passes == 2) {  // half-width rows, every batch swept once per half of k
+            const size_t lds_half = (size_t)4 * (half_scratch_row(t->rw) + 2) * 128;
+            auto kern_half = xmask != 0xffffffffu ? spmm_tiled_k32_half<true> : spmm_tiled_k32_half<false>;
+            kern_half<<<dim3(t->nw / 4), 256, lds_half, s>>>(
+                t->rows, t->rpw, t->nb, t->rw, t->offs, static_cast<const uint32_t*>(t->meta),
+                static_cast<const double*>(t->val), static_cast<const double2*>(x), static_cast<double2*>(y), row_nnz,
+                bar, xmask, spins);
+        } else if (t->meta_bytes == 8)  // 2^24 columns or more
             spmm_tiled_k32<false, double, uint64_t><<<dim3(t->nw / 4), 256, lds, s>>>(
                 t->rows, t->rpw, t->nb, t->rw, t->offs, static_cast<const uint64_t*>(t->meta),
                 static_cast<const double*>(t->val), static_cast<const double2*>(x), static_cast<double2*>(y), row_nnz,

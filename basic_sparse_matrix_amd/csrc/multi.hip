@@ -698,7 +698,7 @@ int bsm_mcsr_plan_info(const bsm_mcsr* m, int* tiled_pieces, int* local_pieces, 
             if (m->prepared && m->schedule != 2 && a->tiled && a->tiled->k == m->k) {
                 ++nt;
                 uint64_t b = 0, w = 0;
-                (void)bsm_tiled_info(a->tiled, &b, nullptr, &w);
+                (void)bsm_tiled_info(a->tiled, &b, nullptr, &w, nullptr, nullptr);
                 bytes += b;
                 pc = w;
             } else if (a->plan_usable && !pc) {

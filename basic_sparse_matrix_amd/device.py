@@ -148,8 +148,11 @@ class TiledPlan:
     def info(self) -> dict:
         lib = _lib.load()
         b, sl, pc = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        _lib.check(lib.bsm_tiled_info(self.handle, ctypes.byref(b), ctypes.byref(sl), ctypes.byref(pc)))
-        return {"bytes": b.value, "slots": sl.value, "panel_cols": pc.value}
+        ps, br = ctypes.c_uint32(), ctypes.c_uint32()
+        _lib.check(lib.bsm_tiled_info(self.handle, ctypes.byref(b), ctypes.byref(sl), ctypes.byref(pc),
+                                      ctypes.byref(ps), ctypes.byref(br)))
+        return {"bytes": b.value, "slots": sl.value, "panel_cols": pc.value, "passes": ps.value,
+                "batch_rows": br.value}
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib._lib is not None:

@@ -416,7 +416,13 @@ int bsm_dev_spmm_panelled(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nn
  * bit for bit (each row still sums in storage order). bsm_dev_tiled_wanted
  * says whether the library would use it for this shape (env BSM_SPMM_TILED:
  * 0 = never, 2 = whenever possible). bsm_tiled_info: bytes of the copy,
- * entry slots (entries + dummies) and the panel width in columns. */
+ * entry slots (entries + dummies), the panel width in columns, the sweeps
+ * per batch of rows (1, or 2: the k = 32 f64 kernel that keeps half-width
+ * rows on chip and runs every batch once per half of k) and the rows per
+ * wave and batch; any of the out pointers may be NULL.
+ * bsm_dev_tiled_half_wanted: whether the copy's model picks the two-sweep
+ * kernel for this shape on a device (or stream) of `cus` compute units; env
+ * BSM_TILED_HALF=0|1 overrides that choice when a copy is built. */
 typedef struct bsm_tiled bsm_tiled;
 #define BSM_TILED_ANY_PADDING 1
 int bsm_dev_tiled_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k,
@@ -426,7 +432,10 @@ int bsm_dev_tiled_create(uint64_t rows, uint64_t n_cols, uint64_t nnz, const int
                          bsm_tiled** out, void* stream);
 int bsm_dev_spmm_tiled(const bsm_tiled* t, const double* x, double* y, int32_t* row_nnz,
                        void* stream);
-int bsm_tiled_info(const bsm_tiled* t, uint64_t* bytes, uint64_t* slots, uint64_t* panel_cols);
+int bsm_dev_tiled_half_wanted(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, uint64_t k,
+                              uint32_t cus);
+int bsm_tiled_info(const bsm_tiled* t, uint64_t* bytes, uint64_t* slots, uint64_t* panel_cols,
+                   uint32_t* passes, uint32_t* batch_rows);
 /* Whether bsm_csr_mul_dense has built (and uses) the tiled copy for this
  * handle; diagnostic. */
 int bsm_csr_tiled(const bsm_csr* m, int* in_use);
