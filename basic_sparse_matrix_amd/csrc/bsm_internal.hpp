@@ -210,6 +210,8 @@ struct bsm_tiled {
     unsigned* bar = nullptr;     // batch arrival counters of the SpMM (one launch at a time per copy)
 };
 
+struct bsm_sym;  // the symmetric copy the refined solve reads (kernels_refine.hip)
+
 // Device-resident finalised Csr<T>.
 struct bsm_csr {
     int dtype = BSM_F64;
@@ -238,6 +240,10 @@ struct bsm_csr {
     // and device index arrays, built on first use (the pattern is immutable),
     // same mutex; released with the handle
     mutable std::shared_ptr<void> nd_plan;
+    // the refined solve's matrix (kernels_refine.hip): the stored entries with
+    // column <= row, mirrored; built on first use, same mutex; released with
+    // the handle
+    mutable bsm_sym* sym = nullptr;
     // row_ptr / col / vals from the result cache (csr_alloc): their block
     // capacities, 0 = plain hipMalloc (bsm_csr_free hipFrees those)
     size_t cache_cap[3] = {0, 0, 0};
@@ -253,7 +259,8 @@ struct bsm_csr {
 // plan (ordering, tree, device index arrays) is shared with the handles and
 // the cache that hold it; the numeric storage is the factor's own.
 struct bsm_nd_factor {
-    int dtype = BSM_F64;
+    int dtype = BSM_F64;      // the factor's own
+    int src_dtype = BSM_F64;  // the factored matrix's (bsm_nd_factor_create_as: it may differ); a refactorisation's must equal it
     int device = 0;
     uint64_t n = 0;
     std::shared_ptr<void> plan;  // NdCached; null for n == 0
@@ -378,7 +385,8 @@ int solve_dispatch_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void*
 int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s);
 // the kept nd factor (kernels_nd.hip); all synchronous on s. b_dev / x_dev:
 // ROW-major n x k, as solve_dispatch_nd's
-int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s);
+// factor_dtype: BSM_F64 or BSM_F32; where it is not a's, a's values are converted first
+int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s);
 // system: BSM_ND_SYS_A / _L / _LT (bsm.h)
 int nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
                     hipStream_t s);
@@ -392,4 +400,13 @@ int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipS
 // the first of them at *first_miss (their vals are 0).
 int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const uint64_t* rows_dev,
                      const uint64_t* cols_dev, void* vals_dev, uint64_t* n_miss, uint64_t* first_miss, hipStream_t s);
+// mixed precision on a kept factor (kernels_refine.hip)
+// n float values into the other float dtype, round-to-nearest (async on s)
+int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s);
+void sym_destroy(bsm_sym* m);
+// The refined solve; the caller has checked a against f (dtype, device,
+// shape) and tol >= 0. b_dev / x_dev: ROW-major n x k of a's dtype (they may
+// be the same array); iters / berr: k host entries or null. Synchronous on s.
+int nd_refine_solve(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b_dev, void* x_dev,
+                    uint32_t max_iter, double tol, uint32_t* iters, double* berr, hipStream_t s);
 }  // namespace bsm

@@ -903,6 +903,7 @@ void bsm_csr_free(bsm_csr* m) {
     rc_release(m->device, m->vals, m->cache_cap[2]);
     if (m->plan_seg) (void)hipFree(m->plan_seg);
     if (m->tiled) tiled_destroy(m->tiled);
+    if (m->sym) sym_destroy(m->sym);
     delete m;
 }
 
@@ -1089,7 +1090,70 @@ int bsm_nd_factor_create(const bsm_csr* a, bsm_nd_factor** out) {
     BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
                 "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
     BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
-    return nd_factor_create(a, out, s);
+    return nd_factor_create(a, a->dtype, out, s);
+}
+
+int bsm_nd_factor_create_as(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out) {
+    BSM_REQUIRE(a && out, BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(factor_dtype == BSM_F64 || factor_dtype == BSM_F32, BSM_ERR_INVALID,
+                "nd factor: factor_dtype must be BSM_F64 or BSM_F32, got %d", factor_dtype);
+    hipStream_t s;
+    BSM_TRY(ctx_stream(&s));
+    BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
+                "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
+    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
+    return nd_factor_create(a, factor_dtype, out, s);
+}
+
+// the refined solve's checks, all before any device is asked for
+static int refine_check(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, const void* x,
+                        double tol) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle (the factor)");
+    BSM_REQUIRE(a, BSM_ERR_INVALID, "null handle (the matrix)");
+    BSM_REQUIRE(tol >= 0.0, BSM_ERR_INVALID, "refined solve: tol must be >= 0 (0 = the default), got %g", tol);
+    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "refined solve: f32/f64 only");
+    BSM_REQUIRE(a->device == f->device, BSM_ERR_INVALID,
+                "refined solve: device differs (the matrix is on device %d, the factor on %d)", a->device, f->device);
+    BSM_REQUIRE(a->rows == f->n && a->cols == f->n, BSM_ERR_DIMENSIONS,
+                "IncorrectDimensions: the matrix is %llu x %llu, the factor's %llu x %llu", (unsigned long long)a->rows,
+                (unsigned long long)a->cols, (unsigned long long)f->n, (unsigned long long)f->n);
+    BSM_REQUIRE(f->n * k == 0 || (b && x), BSM_ERR_INVALID, "null argument (b or x)");
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
+                                    uint32_t max_iter, double tol, uint32_t* iters, double* berr, void* stream) {
+    BSM_TRY(refine_check(f, a, k, b, x, tol));
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return nd_refine_solve(f, a, k, b, x, max_iter, tol, iters, berr, static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                                const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
+                                uint32_t* iters, double* berr) {
+    BSM_TRY(refine_check(f, a, k, b_cols, x_cols, tol));
+    for (uint64_t j = 0; j < k && n && f->n; ++j)
+        BSM_REQUIRE(b_cols[j] && x_cols[j], BSM_ERR_INVALID, "null column pointer %llu", (unsigned long long)j);
+    BSM_REQUIRE(f->n == n, BSM_ERR_PANIC,
+                "solve: b has %llu rows but A has %llu (index out of bounds in the reference)", (unsigned long long)n,
+                (unsigned long long)f->n);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf b, x;
+    BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
+    BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
+    std::vector<uint32_t> it(k);
+    std::vector<double> be(k);
+    BSM_TRY(nd_refine_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), s));
+    BSM_TRY(download_columns(a->dtype, n, k, x.p, x_cols, s));
+    for (uint64_t j = 0; j < k; ++j) {  // the outputs are written together, after everything that can fail
+        if (iters) iters[j] = it[j];
+        if (berr) berr[j] = be[j];
+    }
+    return BSM_OK;
 }
 
 int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* const* b_cols,

@@ -2015,9 +2015,10 @@ int nd_solve_tmp(const NdCached& C, int64_t N, uint64_t k, hipStream_t s, NdSolv
 
 // The numeric factor, first half: the flags cleared and the fronts' input
 // staged (the plain pipeline: zeroed, A assembled, the padding pivots set; the
-// default one: A's values into the per-tile lists' order, in avb)
+// default one: A's values into the per-tile lists' order, in avb). av: A's
+// values as T (a->vals, or their conversion into the factor's dtype)
 template <typename T>
-int nd_stage_fronts(const bsm_csr* a, const NdCached& C, int64_t N, T* F, int* flags, size_t nfl, T* avb,
+int nd_stage_fronts(const bsm_csr* a, const T* av, const NdCached& C, int64_t N, T* F, int* flags, size_t nfl, T* avb,
                     hipStream_t s) {
     const NdPtrs p = nd_ptrs(C);
     BSM_HIP_TRY(hipMemsetAsync(flags, 0, nfl * sizeof(int), s));
@@ -2026,14 +2027,12 @@ int nd_stage_fronts(const bsm_csr* a, const NdCached& C, int64_t N, T* F, int* f
             nd_zero_tiles<T><<<(unsigned)C.n_tiles, 256, 0, s>>>(p.nodes, p.tiles, F);
             BSM_HIP_TRY(hipGetLastError());
         }
-        nd_assemble<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, static_cast<const T*>(a->vals),
-                                                         p.pinv, p.owner, p.nodes, p.st, F);
+        nd_assemble<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, a->row_ptr, a->col, av, p.pinv, p.owner, p.nodes, p.st, F);
         BSM_HIP_TRY(hipGetLastError());
         nd_pad_pivots<T><<<(unsigned)C.nn, 64, 0, s>>>(p.nodes, F);
         BSM_HIP_TRY(hipGetLastError());
     } else if (C.n_aent > 0) {  // A's values in the per-tile lists' order
-        nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(),
-                                                                static_cast<const T*>(a->vals), avb);
+        nd_aent_vals<T><<<nd_blocks(C.n_aent, 256), 256, 0, s>>>(C.n_aent, C.aent.as<int64_t>(), av, avb);
         BSM_HIP_TRY(hipGetLastError());
     }
     return BSM_OK;
@@ -2216,7 +2215,7 @@ int nd_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* 
     int* d_flags = fl.as<int>();
     int* d_status = d_flags + C.n_flags + C.n_levels;
     T* F = fr.as<T>();
-    BSM_TRY(nd_stage_fronts<T>(a, C, N, F, d_flags, nfl, avb.as<T>(), s));
+    BSM_TRY(nd_stage_fronts<T>(a, static_cast<const T*>(a->vals), C, N, F, d_flags, nfl, avb.as<T>(), s));
     stage_mark("nd_assemble", s);
     // BSM_ND_STAMPS=1: nd_factor's per-level cycle stamps, printed after the solve
     DBuf stamps;
@@ -2402,8 +2401,10 @@ int nd_factor_numeric_t(const bsm_csr* a, bsm_nd_factor& f, const NdCached& C, c
     const size_t nfl = (size_t)C.n_flags + (size_t)C.n_levels + 2;
     NdGrid g;
     BSM_TRY(nd_grid<T>(true, false, g));
-    DBuf fl, avb;  // temporaries: the flags, tickets and status; A's values by tile
+    DBuf fl, avb, cvt;  // temporaries: the flags, tickets and status; A's values by tile; A's values as T
     BSM_TRY(fl.alloc(nfl * sizeof(int), s));
+    const bool convert = a->dtype != f.dtype;  // bsm_nd_factor_create_as: the factor's dtype is not the matrix's
+    if (convert) BSM_TRY(cvt.alloc((size_t)std::max<uint64_t>(a->nnz, 1) * sizeof(T), s));
     if (!C.lay.plain) BSM_TRY(avb.alloc((size_t)std::max<int64_t>(C.n_aent, 1) * sizeof(T), s));
     NdDrainOnError drain{s};  // the temporaries go back to the thread's cache only after the kernels
     drain.armed = true;
@@ -2412,7 +2413,9 @@ int nd_factor_numeric_t(const bsm_csr* a, bsm_nd_factor& f, const NdCached& C, c
     // BSM_ND_POISON=1 (tests): the fronts start as NaN (the export may not read what the factor did not write)
     if (opt.poison) BSM_HIP_TRY(hipMemsetAsync(f.fr.p, 0xff, f.fr.bytes, s));
     int* const d_flags = fl.as<int>();
-    BSM_TRY(nd_stage_fronts<T>(a, C, N, f.fr.as<T>(), d_flags, nfl, avb.as<T>(), s));
+    if (convert) BSM_TRY(convert_values(a->dtype, f.dtype, a->nnz, a->vals, cvt.p, s));
+    const T* const av = convert ? cvt.as<T>() : static_cast<const T*>(a->vals);
+    BSM_TRY(nd_stage_fronts<T>(a, av, C, N, f.fr.as<T>(), d_flags, nfl, avb.as<T>(), s));
     stage_mark("nd_assemble", s);
     BSM_TRY(nd_factor_levels<T>(C, g, f.fr.as<T>(), f.dv.as<T>(), d_flags, avb.as<T>(), (T*)nullptr,
                                 (const T*)nullptr, nullptr, s));
@@ -2926,17 +2929,19 @@ int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const 
                : nd_factor_selinv_t<float>(*f, diag_dev, nq, rows_dev, cols_dev, vals_dev, n_miss, first_miss, s);
 }
 
-int nd_factor_create(const bsm_csr* a, bsm_nd_factor** out, hipStream_t s) {
+int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s) {
     BSM_REQUIRE(a->rows < ((uint64_t)1 << 31), BSM_ERR_UNSUPPORTED, "solve nd: n >= 2^31");
+    BSM_REQUIRE(a->dtype == BSM_F64 || a->dtype == BSM_F32, BSM_ERR_INVALID, "solve: f32/f64 only");
     auto f = std::make_unique<bsm_nd_factor>();
-    f->dtype = a->dtype;
+    f->dtype = factor_dtype;
+    f->src_dtype = a->dtype;
     f->device = a->device;
     f->n = a->rows;
     if (a->rows > 0) {
         int rc = BSM_ERR_INVALID;
-        if (a->dtype == BSM_F64) rc = nd_factor_create_t<double>(a, *f, s);
-        else if (a->dtype == BSM_F32) rc = nd_factor_create_t<float>(a, *f, s);
-        else set_error("solve: f32/f64 only");
+        if (factor_dtype == BSM_F64) rc = nd_factor_create_t<double>(a, *f, s);
+        else if (factor_dtype == BSM_F32) rc = nd_factor_create_t<float>(a, *f, s);
+        else set_error("nd factor: factor_dtype must be BSM_F64 or BSM_F32, got %d", factor_dtype);
         if (rc != BSM_OK) return rc;
     }
     *out = f.release();
@@ -2951,7 +2956,10 @@ int nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a, hipStream_t s) {
     BSM_REQUIRE(a->device == f->device, BSM_ERR_INVALID,
                 "nd factor refactor: device differs (the matrix is on device %d, the factor on %d)", a->device,
                 f->device);
-    BSM_REQUIRE(a->dtype == f->dtype, BSM_ERR_INVALID, "nd factor refactor: dtype differs from the factored matrix's");
+    BSM_REQUIRE(a->dtype == f->src_dtype, BSM_ERR_INVALID,
+                "nd factor refactor: dtype differs from the factored matrix's (%s was factored, the matrix is %s)",
+                f->src_dtype == BSM_F64 ? "f64" : "f32",
+                a->dtype == BSM_F64 ? "f64" : a->dtype == BSM_F32 ? "f32" : "not a float");
     BSM_REQUIRE(a->rows == f->n && a->cols == f->n, BSM_ERR_INVALID,
                 "nd factor refactor: n differs (the matrix is %llu x %llu, the factor's %llu x %llu)",
                 (unsigned long long)a->rows, (unsigned long long)a->cols, (unsigned long long)f->n,

@@ -9,6 +9,7 @@ this build's addition.
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -95,6 +96,51 @@ def _check_factorable(a: Csr, what: str):
         raise Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix")
 
 
+@dataclass
+class RefineInfo:
+    """What a refined solve reports per right-hand column: the corrections
+    made, the backward error of the returned iterate, whether it is at or
+    below ``tol``, and the ``tol`` that was used."""
+
+    iters: np.ndarray  # uint32 [k]
+    berr: np.ndarray  # float64 [k]
+    converged: np.ndarray  # bool [k]
+    tol: float
+
+
+def refine_default_tol(a: Csr) -> float:
+    """``(m + 2) 2^-53`` with ``m`` the longest row of ``a``'s lower triangle
+    mirrored: the rounding bound of the f64 residual itself, the library's
+    default for ``tol == 0``."""
+    rp, ci, _ = a._csr_arrays()
+    n = a.dims.rows
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp.astype(np.int64)))
+    cols = ci.astype(np.int64)
+    m = np.bincount(rows[cols <= rows], minlength=n) + np.bincount(cols[cols < rows], minlength=n)
+    return float((int(m.max()) if n else 0) + 2) * 2.0 ** -53
+
+
+def check_refine_args(a: Csr, b_dtype, max_iter, tol, what: str) -> None:
+    """The host-side checks the refined solves share."""
+    if a.dtype not in _FLOATS:
+        raise TypeError(f"{what}: needs Csr<f32> (or f64), got {a.dtype}")
+    if np.dtype(b_dtype) != a.dtype:
+        raise TypeError(f"{what}: b must have a's dtype {a.dtype}, got {np.dtype(b_dtype)}")
+    if int(max_iter) != max_iter or max_iter < 0:
+        raise ValueError(f"{what}: max_iter must be an integer >= 0, got {max_iter!r}")
+    if tol is not None and not tol > 0:  # a NaN is refused here too
+        raise ValueError(f"{what}: tol must be > 0 (None = the default), got {tol!r}")
+
+
+def refine_tol_in_use(a: Csr, dev, tol) -> float:
+    """``tol``, or the default for ``a``, computed once per device handle."""
+    if tol is not None:
+        return float(tol)
+    if dev.refine_tol is None:
+        dev.refine_tol = refine_default_tol(a)
+    return dev.refine_tol
+
+
 class NdFactor:
     """The nested-dissection Cholesky factor of ``P A P^T``, kept on the
     device (``bsm_nd_factor``): factor once with :func:`cholesky_nd`, then
@@ -102,7 +148,10 @@ class NdFactor:
     ``logdet()`` out, and ``refactor`` new values of the same pattern in
     place (``device.nd_factor_solve`` solves on device tensors), and read the
     selected inverse (``inv_diag()``, ``inv_entries()``, ``inv_on()``:
-    ``A^-1`` on the pattern of ``L + L^T``). The handle owns its
+    ``A^-1`` on the pattern of ``L + L^T``). ``solve_refined`` refines a
+    solve with f64 residuals and reports its backward error; the factor's
+    dtype may be chosen apart from the matrix's
+    (``cholesky_nd(a, factor_dtype=...)``). The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
@@ -147,6 +196,42 @@ class NdFactor:
         _raise_for(lib.bsm_nd_factor_solve_system(self._h(), sys_code, k, n, _lib.ptr_array(b_cols),
                                                   _lib.ptr_array(out.data)))
         return out
+
+    def solve_refined(self, a: Csr, b: Dense, *, max_iter: int = 5, tol: float | None = None):
+        """Iterative refinement on this factor (``bsm_nd_factor_solve_refined``):
+        ``x_0 = M^-1 b`` by the factor, then up to ``max_iter`` corrections
+        from residuals ``b - S x`` formed in f64, each column on its own.
+        ``a`` is the system's matrix (f32 or f64; its lower triangle mirrored,
+        as the factor reads it), ``b`` a ``Dense`` of ``a``'s dtype; the factor
+        may have either dtype, and ``a`` may be the factored matrix or one
+        near it. Returns ``(x, RefineInfo)``: ``x`` of ``a``'s dtype, the
+        iterate with the smallest backward error ``berr``, after ``iters``
+        corrections. ``tol=None`` is the default ``(m + 2) 2^-53``, ``m`` the
+        longest row of the mirrored matrix. An f32 factor of an f64 matrix
+        (``cholesky_nd(a, factor_dtype=np.float32)``) reaches f64 backward
+        error in two or three corrections."""
+        h = self._h()
+        dims = b.get_dims()
+        n, k = dims.rows, dims.cols
+        check_refine_args(a, b.dtype if k else a.dtype, max_iter, tol, "NdFactor.solve_refined")
+        if a.dims.rows != self.n or a.dims.cols != self.n or n != self.n:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        b_cols = []
+        for j in range(k):
+            c = np.ascontiguousarray(b.get_col(j))
+            if c.shape[0] < n:
+                raise Panic(f"index out of bounds: the len is {c.shape[0]} but the index is {c.shape[0]}")
+            b_cols.append(np.ascontiguousarray(c[:n]))
+        dev = a._device()
+        tol_used = refine_tol_in_use(a, dev, tol)
+        lib = _lib.require_device()
+        out = Dense.new_default_with_dims(k, n, dtype=a.dtype)
+        iters = np.zeros(k, dtype=np.uint32)
+        berr = np.zeros(k, dtype=np.float64)
+        _raise_for(lib.bsm_nd_factor_solve_refined(h, dev.handle, k, n, _lib.ptr_array(b_cols),
+                                                   _lib.ptr_array(out.data), max_iter, tol_used, _lib.ptr(iters),
+                                                   _lib.ptr(berr)))
+        return out, RefineInfo(iters, berr, berr <= tol_used, tol_used)
 
     def refactor(self, a: Csr) -> None:
         """New values on the same pattern (``bsm_nd_factor_refactor``): the
@@ -284,16 +369,28 @@ class NdFactor:
         self.close()
 
 
-def cholesky_nd(a: Csr) -> NdFactor:
+def cholesky_nd(a: Csr, factor_dtype=None) -> NdFactor:
     """Analysis (through the plan caches of ``solve(order="nd")``) and numeric
     factorisation of ``P A P^T`` (``bsm_nd_factor_create``), kept as an
     :class:`NdFactor`. The same type and shape checks as :func:`solve`; a
-    matrix that is not positive definite is reported here."""
+    matrix that is not positive definite is reported here.
+
+    ``factor_dtype`` (``np.float32`` or ``np.float64``; ``None`` = ``a``'s)
+    chooses the dtype the factor is computed and stored in
+    (``bsm_nd_factor_create_as``): an f32 factor of an f64 matrix has half the
+    bytes and the bits of ``cholesky_nd`` on the matrix rounded to f32;
+    ``NdFactor.solve_refined`` brings its solves back to f64 accuracy."""
     _check_factorable(a, "cholesky_nd")
+    if factor_dtype is not None and np.dtype(factor_dtype) not in _FLOATS:
+        raise TypeError(f"cholesky_nd: factor_dtype must be float32 or float64, got {np.dtype(factor_dtype)}")
     dev = a._device()
     lib = _lib.require_device()
     out = ctypes.c_void_p()
-    _raise_for(lib.bsm_nd_factor_create(dev.handle, ctypes.byref(out)))
+    if factor_dtype is None:
+        _raise_for(lib.bsm_nd_factor_create(dev.handle, ctypes.byref(out)))
+    else:
+        _raise_for(lib.bsm_nd_factor_create_as(dev.handle, _lib.DTYPE_CODES[np.dtype(factor_dtype)],
+                                               ctypes.byref(out)))
     return NdFactor(out.value)
 
 

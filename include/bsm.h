@@ -314,6 +314,54 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    device (n values of its dtype), on `stream`; returns after the stream has
  *    drained. The same kernels and bits as bsm_nd_factor_selinv's diag. A null
  *    f, or a null diag with n > 0 -> BSM_ERR_INVALID.
+ *  - bsm_nd_factor_create_as: bsm_nd_factor_create with the factor's dtype
+ *    chosen: factor_dtype is BSM_F64 or BSM_F32 (anything else ->
+ *    BSM_ERR_INVALID, before any device is asked for). Equal to a's dtype it
+ *    IS bsm_nd_factor_create. Otherwise a's values are converted once
+ *    (round-to-nearest) into a temporary of the factor's dtype and the same
+ *    numeric path runs on them: the f32 factor of an f64 matrix has the bits
+ *    of bsm_nd_factor_create on that matrix rounded to f32, and half the f64
+ *    factor's bsm_nd_factor_info bytes. The plan and the caches know no dtype
+ *    and are shared as ever. bsm_nd_factor_info reports the FACTOR's dtype,
+ *    in which solve, solve_system, export, logdet and selinv work; the handle
+ *    remembers the matrix's, which bsm_nd_factor_refactor's matrix must have
+ *    (it is converted the same way).
+ *  - bsm_nd_factor_solve_refined: iterative refinement on the kept factor
+ *    (what xPORFS / DSPOSV do): x_0 = M^-1 b by the factor, then corrections
+ *    x += M^-1 r from residuals r = b - S x formed in f64, for each of the k
+ *    columns on its own. `a` is the system's matrix, n x n on f's device, f32
+ *    or f64; b_cols / x_cols are host columns of a's dtype; f may have either
+ *    dtype. The system solved is S x = b with S[i][j] = A[max(i,j)][min(i,j)]
+ *    over a's stored entries with column <= row: the matrix the factor reads
+ *    (entries above the diagonal are ignored). `a` is not compared with the
+ *    factored matrix: it may be a nearby one (a stale factor), and the loop
+ *    then converges as fast as M^-1 S is close to I. The backward error
+ *      omega_j = ||r_j||inf / (||S||inf ||x_j||inf + ||b_j||inf)
+ *    is computed after every solve; a column goes on while omega_j > tol and
+ *    omega_j <= half the one before (LAPACK's stagnation rule), for at most
+ *    max_iter corrections; x_j is the iterate with the smallest omega_j, which
+ *    berr[j] reports, after iters[j] corrections (both host arrays of k, or
+ *    NULL). tol == 0: the default (m + 2) 2^-53, m the longest row of S, the
+ *    rounding bound of the f64 residual itself; tol < 0 or NaN ->
+ *    BSM_ERR_INVALID. Right-hand sides and residuals are scaled by a power of
+ *    two into [1, 2) before they are cast to the factor's dtype (exact, so a
+ *    residual of 1e-13 ||b|| stays normal in f32). b_j == 0 gives x_j = 0,
+ *    berr 0, iters 0; a non-finite omega stops its column. BSM_OK whether or
+ *    not the columns converged: berr[j] <= tol says so. Column j's x, iters
+ *    and berr depend neither on k nor on the other columns, and the same call
+ *    gives the same bits (fixed summation order, no floating-point atomics);
+ *    with max_iter == 0 and a's dtype the factor's, x has the bits of
+ *    bsm_nd_factor_solve. Errors, all before any device work and with every
+ *    output untouched: a null f or a, or a null among b / x with n k > 0 ->
+ *    BSM_ERR_INVALID ("null ..."); a not f32 / f64, or on another device ->
+ *    BSM_ERR_INVALID; a not n x n -> BSM_ERR_DIMENSIONS; n != rows ->
+ *    BSM_ERR_PANIC as bsm_nd_factor_solve; a handle without values ->
+ *    BSM_ERR_INVALID as for the solves. S is built on the first call and kept
+ *    on `a` until bsm_csr_free (row_ptr int64, columns int32, values of a's
+ *    dtype: about a's own size).
+ *  - bsm_dev_nd_factor_solve_refined: the same with b and x in HBM on the
+ *    factor's device, ROW-major n x k of a's dtype (x may be b), on `stream`;
+ *    synchronous for that stream. The same kernels and bits as the host call.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -334,6 +382,12 @@ int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, cons
 int bsm_nd_factor_selinv(const bsm_nd_factor* f, void* diag, uint64_t nq, const uint64_t* rows,
                          const uint64_t* cols, void* vals);
 int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream);
+int bsm_nd_factor_create_as(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out);
+int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                                const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
+                                uint32_t* iters, double* berr);
+int bsm_dev_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
+                                    uint32_t max_iter, double tol, uint32_t* iters, double* berr, void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

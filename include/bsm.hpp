@@ -752,6 +752,38 @@ Dense<T> solve_nd(Csr<T> a, Dense<T> b) {
 /// The system an NdFactor solves (BSM_ND_SYS_*).
 enum class NdSystem : int { A = BSM_ND_SYS_A, L = BSM_ND_SYS_L, Lt = BSM_ND_SYS_LT };
 
+/// What NdFactor::solve_refined returns: x (the iterate with the smallest
+/// backward error), and per right-hand column the corrections made, that
+/// backward error, whether it is at or below tol, and the tol in use.
+template <class T>
+struct Refined {
+    Dense<T> x;
+    std::vector<uint32_t> iters;
+    std::vector<double> berr;
+    std::vector<bool> converged;
+    double tol = 0.0;
+};
+
+namespace detail {
+/// (m + 2) 2^-53, m the longest row of a's lower triangle mirrored: the
+/// library's default tol (the rounding bound of the f64 residual itself).
+template <class T>
+double refine_default_tol(const Csr<T>& a) {
+    const size_t n = a.get_dims().rows;
+    std::vector<uint64_t> len(n, 0);
+    const auto& rp = a.row_index();
+    const auto& ci = a.col_index();
+    for (size_t i = 0; i < n; ++i)
+        for (size_t e = rp[i]; e < rp[i + 1]; ++e) {
+            if (ci[e] <= i) ++len[i];
+            if (ci[e] < i) ++len[ci[e]];
+        }
+    uint64_t m = 0;
+    for (uint64_t l : len) m = std::max(m, l);
+    return (double)(m + 2) * 0x1p-53;
+}
+}  // namespace detail
+
 /// The factor of solve_nd, kept (bsm_nd_factor; this build's addition): the
 /// constructor analyses and factors P A P^T once (a non-square `a` panics,
 /// one that is not positive definite throws DeviceError), solve() runs only
@@ -773,14 +805,34 @@ public:
         detail::check(bsm_nd_factor_info(f, &n_, nullptr, nullptr, nullptr));
     }
 
+    /// The factor in dtype T of a matrix of another float dtype
+    /// (bsm_nd_factor_create_as; see cholesky_nd_as): a's values are rounded
+    /// to T once, and the factor has the bits of NdFactor<T> on that matrix.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    static NdFactor from_matrix_of(const Csr<U>& a) {
+        if (a.get_dims().rows != a.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        auto h = a.device();
+        bsm_nd_factor* f = nullptr;
+        detail::check(bsm_nd_factor_create_as(h.get(), detail::dtype_of<T>::value, &f));
+        NdFactor out;
+        out.f_.reset(f);
+        detail::check(bsm_nd_factor_info(f, &out.n_, nullptr, nullptr, nullptr));
+        return out;
+    }
+
     size_t rows() const { return n_; }
 
     /// New values on the same pattern (bsm_nd_factor_refactor): afterwards the
-    /// factor has the bits of NdFactor(a). Another dtype is a compile error;
-    /// another shape or pattern throws and leaves the factor untouched. Values
+    /// factor has the bits of NdFactor(a) (of cholesky_nd_as<T>(a) for a
+    /// matrix of the other float dtype). A dtype other than the factored
+    /// matrix's, another shape or pattern throws and leaves the factor untouched. Values
     /// that are not positive definite throw DeviceError and leave the handle
     /// without a factor until a later refactor succeeds.
-    void refactor(const Csr<T>& a) {
+    template <class U>
+        requires std::is_floating_point_v<U>
+    void refactor(const Csr<U>& a) {
         if (a.get_dims().rows != a.get_dims().cols)
             throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
         auto h = a.device();
@@ -808,6 +860,34 @@ public:
         }
         detail::check(bsm_nd_factor_solve_system(f_.get(), static_cast<int>(system), k, n, in_cols.data(),
                                                  out_cols.data()));
+        return out;
+    }
+
+    /// Iterative refinement on this factor (bsm_nd_factor_solve_refined):
+    /// x_0 = M^-1 b, then up to max_iter corrections from f64 residuals of
+    /// S x = b, S being a's lower triangle mirrored; every column on its own.
+    /// `a` (f32 or f64, the factored matrix or one near it) and b share a
+    /// dtype, which need not be the factor's. tol == 0: (m + 2) 2^-53, m the
+    /// longest row of S. a or b of another shape: Panic (IncorrectDimensions).
+    template <class U>
+        requires std::is_floating_point_v<U>
+    Refined<U> solve_refined(const Csr<U>& a, const Dense<U>& b, unsigned max_iter = 5, double tol = 0) const {
+        const size_t n = b.get_dims().rows, k = b.get_dims().cols;
+        if (!(tol >= 0)) throw std::invalid_argument("NdFactor::solve_refined: tol must be >= 0 (0 = the default)");
+        if (a.get_dims().rows != n_ || a.get_dims().cols != n_ || n != n_)
+            throw Panic("NdFactor::solve_refined: IncorrectDimensions");
+        Refined<U> out{Dense<U>::new_default_with_dims(k, n), std::vector<uint32_t>(k), std::vector<double>(k),
+                       std::vector<bool>(k), tol > 0 ? tol : detail::refine_default_tol(a)};
+        std::vector<const void*> in_cols(k);
+        std::vector<void*> out_cols(k);
+        for (size_t j = 0; j < k; ++j) {
+            in_cols[j] = b.get_col(j).data();
+            out_cols[j] = out.x.get_col_mut(j).data();
+        }
+        auto h = a.device();
+        detail::check(bsm_nd_factor_solve_refined(f_.get(), h.get(), k, n, in_cols.data(), out_cols.data(), max_iter,
+                                                  out.tol, out.iters.data(), out.berr.data()));
+        for (size_t j = 0; j < k; ++j) out.converged[j] = out.berr[j] <= out.tol;
         return out;
     }
 
@@ -858,12 +938,22 @@ public:
     }
 
 private:
+    NdFactor() = default;
     struct Free {
         void operator()(bsm_nd_factor* p) const { bsm_nd_factor_free(p); }
     };
     std::unique_ptr<bsm_nd_factor, Free> f_;
     uint64_t n_ = 0;
 };
+
+/// The nd factor of `a` computed and kept in dtype F (this build's addition):
+/// an f32 factor of an f64 matrix has half the bytes; NdFactor::solve_refined
+/// brings its solves back to f64 accuracy.
+template <class F, class T>
+    requires std::is_floating_point_v<F> && std::is_floating_point_v<T>
+NdFactor<F> cholesky_nd_as(const Csr<T>& a) {
+    return NdFactor<F>::from_matrix_of(a);
+}
 
 }  // namespace bsm
 

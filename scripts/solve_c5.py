@@ -410,6 +410,65 @@ def nd_factor_ops(f, A, B, reps, pattern, kernel_stats=None):
     }
 
 
+def nd_refine_ops(A, B, reps, f64_nbytes):
+    """The mixed-precision path on an f64 system, host wall ms around
+    synchronous calls. factor_f32_ms: cholesky_nd(A, factor_dtype=float32) on
+    the warm handle (the values converted inside the clock); refined_ms:
+    device.nd_factor_solve_refined on that factor with the f64 A, one column,
+    b and x resident in HBM (A's symmetric copy built by the warm-up call),
+    with its iters and berr; refined_no_correction_ms: the same with
+    max_iter=0 (one solve, one residual); solve_dev_f32_ms: the f32 factor's
+    plain device solve; resid_ms / update_ms / judge_ms: the last iteration's
+    residual pass, iterate update and reduction between their stage marks
+    (0 when the stage timer is off); nbytes of both factors."""
+    import torch
+
+    from basic_sparse_matrix_amd import cholesky_nd, device
+
+    t_factor = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f = cholesky_nd(A, factor_dtype=np.float32)
+        t_factor.append(time.perf_counter() - t0)
+        f.close()
+    f = cholesky_nd(A, factor_dtype=np.float32)
+    bd = torch.tensor(np.ascontiguousarray(B.get_col(0)), device="cuda")
+    xd = torch.empty_like(bd)
+    b32 = bd.to(torch.float32)
+    x32 = torch.empty_like(b32)
+    t0 = time.perf_counter()
+    _, info = device.nd_factor_solve_refined(f, A, bd, out=xd)  # builds A's symmetric copy
+    first_ms = 1e3 * (time.perf_counter() - t0)
+    count = max(5 * reps, 10)
+    t_ref, t_ref0, t_plain, st = [], [], [], []
+    for _ in range(count):
+        t0 = time.perf_counter()
+        _, info = device.nd_factor_solve_refined(f, A, bd, out=xd)
+        t_ref.append(time.perf_counter() - t0)
+        st.append(_lib.stage_times())
+        t0 = time.perf_counter()
+        device.nd_factor_solve_refined(f, A, bd, out=xd, max_iter=0)
+        t_ref0.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        device.nd_factor_solve(f, b32, out=x32)
+        t_plain.append(time.perf_counter() - t0)
+    nbytes = f.nbytes
+    f.close()
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    mm = lambda t: [round(1e3 * min(t), 3), round(1e3 * max(t), 3)]  # noqa: E731
+    stage = lambda k: round(float(np.median([s.get(k, 0.0) for s in st])), 4)  # noqa: E731
+    return {
+        "factor_f32_ms": med(t_factor), "factor_f32_ms_min_max": mm(t_factor),
+        "refined_ms": med(t_ref), "refined_ms_min_max": mm(t_ref), "refined_calls": len(t_ref),
+        "refined_first_call_ms": round(first_ms, 3),
+        "refined_iters": int(info.iters[0]), "refined_berr": float(info.berr[0]), "refined_tol": info.tol,
+        "refined_converged": bool(info.converged[0]),
+        "refined_no_correction_ms": med(t_ref0), "solve_dev_f32_ms": med(t_plain),
+        "resid_ms": stage("refine_resid"), "update_ms": stage("refine_update"), "judge_ms": stage("refine_judge"),
+        "factor_f32_nbytes": nbytes, "factor_f64_nbytes": f64_nbytes,
+    }
+
+
 def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused, pattern):
     """The kept factor (cholesky_nd / NdFactor) on the same system: host wall
     clock around synchronous calls. factor_ms: cholesky_nd on the warm handle
@@ -472,7 +531,10 @@ def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused, pattern):
                                         / np.linalg.norm(np.asarray(x_fused, np.float64))),
     }
     out.update(nd_factor_ops(f, A, B, reps, pattern, args.kernel_stats))
+    f64_nbytes = f.nbytes
     f.close()
+    if args.dtype == "f64":  # the mixed-precision path: an f32 factor of this matrix, refined
+        out.update(nd_refine_ops(A, B, reps, f64_nbytes))
     return out
 
 
