@@ -120,6 +120,8 @@ SIGNATURES = [
     ("bsm_nd_factor_create_as", _int, [_vp, _int, ctypes.POINTER(_vp)]),
     ("bsm_nd_factor_solve_refined", _int, [_vp, _vp, _u64, _u64, _pp, _pp, _u32, ctypes.c_double, _vp, _vp]),
     ("bsm_dev_nd_factor_solve_refined", _int, [_vp, _vp, _u64, _vp, _vp, _u32, ctypes.c_double, _vp, _vp, _vp]),
+    ("bsm_nd_factor_solve_pcg", _int, [_vp, _vp, _u64, _u64, _pp, _pp, _u32, ctypes.c_double, _vp, _vp, _vp]),
+    ("bsm_dev_nd_factor_solve_pcg", _int, [_vp, _vp, _u64, _vp, _vp, _u32, ctypes.c_double, _vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),

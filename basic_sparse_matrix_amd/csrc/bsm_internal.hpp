@@ -210,7 +210,16 @@ struct bsm_tiled {
     unsigned* bar = nullptr;     // batch arrival counters of the SpMM (one launch at a time per copy)
 };
 
-struct bsm_sym;  // the symmetric copy the refined solve reads (kernels_refine.hip)
+// The symmetric copy of a handle (bsm_csr::sym), which the refined and the
+// pcg solves read (kernels_refine.hip builds it).
+struct bsm_sym {
+    int64_t* rp = nullptr;   // n + 1
+    int32_t* col = nullptr;  // nnz, ascending inside a row whenever a's rows are
+    void* vals = nullptr;    // nnz values of a's dtype
+    uint64_t nnz = 0;
+    double norm_inf = 0.0;  // ||S||inf: the largest row sum of |values|
+    uint64_t max_len = 0;   // m: the longest row
+};
 
 // Device-resident finalised Csr<T>.
 struct bsm_csr {
@@ -409,4 +418,47 @@ void sym_destroy(bsm_sym* m);
 // be the same array); iters / berr: k host entries or null. Synchronous on s.
 int nd_refine_solve(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b_dev, void* x_dev,
                     uint32_t max_iter, double tol, uint32_t* iters, double* berr, hipStream_t s);
+
+// What the refined solve shares with the pcg solve (kernels_pcg.hip).
+using ull = unsigned long long;
+
+// |v| as an integer: ordered as the values are, every NaN above +inf
+__device__ __forceinline__ ull abs_bits(double v) { return (ull)__double_as_longlong(fabs(v)); }
+__device__ __forceinline__ double bits_abs(ull b) { return __longlong_as_double((long long)b); }
+__device__ __forceinline__ ull umax(ull a, ull b) { return a > b ? a : b; }
+
+struct DrainOnError {  // cached temporaries go back only after the kernels that use them
+    hipStream_t s;
+    bool armed = true;
+    ~DrainOnError() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+
+constexpr unsigned REFINE_MAX_BLOCKS = 1024;  // the partials one workgroup reduces
+
+struct RefineCol;  // refine_rule.hpp
+// the handle's symmetric copy, built on first use
+int sym_obtain(const bsm_csr* a, hipStream_t s, const bsm_sym** out);
+// lanes per row of refine_resid, and its workgroups (properties of S and n alone)
+int resid_group(const bsm_sym* S, int64_t n);
+unsigned resid_blocks(int g, int64_t n);
+// The refined solve's first iterate, by its own kernels: B = (double)b, st =
+// the columns' ||b||inf and scales, X = scale M^-1 cast(B / scale), R = B - S X,
+// part = refine_resid's maxima of |r| and |x| ([block][2][k], *nb blocks). W:
+// n k values of the factor's dtype. Async on s past the solve.
+int refine_first_iterate(const bsm_nd_factor* f, const bsm_csr* a, const bsm_sym* S, int64_t n, int64_t k,
+                         const void* b_dev, double* B, double* X, double* R, void* W, ull* part, RefineCol* st,
+                         unsigned* nb, hipStream_t s);
+// W = M^-1 cast(V / scale) on st's active columns, zeros on the others
+// (refine_scale_cast, then the factor's A-system solve in place)
+int refine_precondition(const bsm_nd_factor* f, int64_t n, int64_t k, const double* V, const RefineCol* st, void* W,
+                        hipStream_t s);
+// R = B - S X with its partial maxima (refine_resid)
+int refine_residual(const bsm_csr* a, const bsm_sym* S, int64_t n, int64_t k, const double* X, const double* B,
+                    double* R, ull* part, unsigned* nb, hipStream_t s);
+// The pcg solve (kernels_pcg.hip); arguments and checks as nd_refine_solve's,
+// flags: k host entries or null (bit 0: the column broke down).
+int nd_pcg_solve(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b_dev, void* x_dev,
+                 uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags, hipStream_t s);
 }  // namespace bsm

@@ -1156,6 +1156,43 @@ int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64
     return BSM_OK;
 }
 
+int bsm_dev_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
+                                uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags,
+                                void* stream) {
+    BSM_TRY(refine_check(f, a, k, b, x, tol));
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return nd_pcg_solve(f, a, k, b, x, max_iter, tol, iters, berr, flags, static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                            const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
+                            uint32_t* iters, double* berr, uint32_t* flags) {
+    BSM_TRY(refine_check(f, a, k, b_cols, x_cols, tol));
+    for (uint64_t j = 0; j < k && n && f->n; ++j)
+        BSM_REQUIRE(b_cols[j] && x_cols[j], BSM_ERR_INVALID, "null column pointer %llu", (unsigned long long)j);
+    BSM_REQUIRE(f->n == n, BSM_ERR_PANIC,
+                "solve: b has %llu rows but A has %llu (index out of bounds in the reference)", (unsigned long long)n,
+                (unsigned long long)f->n);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf b, x;
+    BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
+    BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
+    std::vector<uint32_t> it(k), fl(k);
+    std::vector<double> be(k);
+    BSM_TRY(nd_pcg_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), fl.data(), s));
+    BSM_TRY(download_columns(a->dtype, n, k, x.p, x_cols, s));
+    for (uint64_t j = 0; j < k; ++j) {  // the outputs are written together, after everything that can fail
+        if (iters) iters[j] = it[j];
+        if (berr) berr[j] = be[j];
+        if (flags) flags[j] = fl[j];
+    }
+    return BSM_OK;
+}
+
 int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* const* b_cols,
                                void* const* x_cols) {
     BSM_REQUIRE(f && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");

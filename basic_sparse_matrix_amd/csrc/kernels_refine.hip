@@ -18,37 +18,12 @@
 #include "bsm_internal.hpp"
 #include "refine_rule.hpp"
 
-// The symmetric copy of a handle (bsm_csr::sym).
-struct bsm_sym {
-    int64_t* rp = nullptr;   // n + 1
-    int32_t* col = nullptr;  // nnz, ascending inside a row whenever a's rows are
-    void* vals = nullptr;    // nnz values of a's dtype
-    uint64_t nnz = 0;
-    double norm_inf = 0.0;  // ||S||inf: the largest row sum of |values|
-    uint64_t max_len = 0;   // m: the longest row
-};
-
 namespace bsm {
 namespace {
-
-using ull = unsigned long long;
 
 inline unsigned blocks_for(uint64_t n, unsigned b, uint64_t cap = 0x7fffffffu) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + b - 1) / b, cap));
 }
-
-// |v| as an integer: ordered as the values are, every NaN above +inf
-__device__ __forceinline__ ull abs_bits(double v) { return (ull)__double_as_longlong(fabs(v)); }
-__device__ __forceinline__ double bits_abs(ull b) { return __longlong_as_double((long long)b); }
-__device__ __forceinline__ ull umax(ull a, ull b) { return a > b ? a : b; }
-
-struct DrainOnError {  // cached temporaries go back only after the kernels that use them
-    hipStream_t s;
-    bool armed = true;
-    ~DrainOnError() {
-        if (armed) (void)hipStreamSynchronize(s);
-    }
-};
 
 // ---- values into another float dtype ---------------------------------------
 // four values per thread: 2 x 16 bytes of f64 against 16 bytes of f32,
@@ -232,21 +207,7 @@ int sym_build(const bsm_csr* a, hipStream_t s, bsm_sym** out) {
     return BSM_OK;
 }
 
-// the handle's symmetric copy, built on first use
-int sym_obtain(const bsm_csr* a, hipStream_t s, const bsm_sym** out) {
-    std::lock_guard<std::mutex> lk(a->plan_mu);
-    if (!a->sym) {
-        bsm_sym* m = nullptr;
-        BSM_TRY(sym_build(a, s, &m));
-        a->sym = m;
-    }
-    *out = a->sym;
-    return BSM_OK;
-}
-
 // ---- the refinement's kernels ----------------------------------------------
-constexpr unsigned REFINE_MAX_BLOCKS = 1024;  // the partials one workgroup reduces
-
 // B = (double)b, and per workgroup and column max |b|: part[block][j]
 template <typename TA>
 __global__ __launch_bounds__(256) void refine_load(int64_t n, int64_t k, const TA* __restrict__ b,
@@ -448,14 +409,6 @@ int resid_launch_g(unsigned nb, int64_t n, int64_t k, const bsm_sym* S, const do
     return BSM_OK;
 }
 
-// lanes per row from S's mean row length (a property of the matrix alone, so
-// a column's sums do not move with k)
-inline int resid_group(const bsm_sym* S, int64_t n) {
-    const uint64_t mean = S->nnz / (uint64_t)std::max<int64_t>(n, 1);
-    return mean <= 4 ? 4 : mean <= 8 ? 8 : mean <= 16 ? 16 : 64;
-}
-inline unsigned resid_blocks(int g, int64_t n) { return blocks_for((uint64_t)n, 256u / (unsigned)g, REFINE_MAX_BLOCKS); }
-
 template <typename TA>
 int resid_launch(int64_t n, int64_t k, const bsm_sym* S, const double* X, const double* B, double* R, ull* part,
                  unsigned* nb_out, hipStream_t s) {
@@ -522,6 +475,73 @@ int refine_t(const bsm_nd_factor* f, const bsm_sym* S, int64_t n, int64_t k, con
 }  // namespace
 
 void sym_destroy(bsm_sym* m) { sym_free(m); }
+
+// the handle's symmetric copy, built on first use
+int sym_obtain(const bsm_csr* a, hipStream_t s, const bsm_sym** out) {
+    std::lock_guard<std::mutex> lk(a->plan_mu);
+    if (!a->sym) {
+        bsm_sym* m = nullptr;
+        BSM_TRY(sym_build(a, s, &m));
+        a->sym = m;
+    }
+    *out = a->sym;
+    return BSM_OK;
+}
+
+// lanes per row from S's mean row length (a property of the matrix alone, so
+// a column's sums do not move with k)
+int resid_group(const bsm_sym* S, int64_t n) {
+    const uint64_t mean = S->nnz / (uint64_t)std::max<int64_t>(n, 1);
+    return mean <= 4 ? 4 : mean <= 8 ? 8 : mean <= 16 ? 16 : 64;
+}
+unsigned resid_blocks(int g, int64_t n) { return blocks_for((uint64_t)n, 256u / (unsigned)g, REFINE_MAX_BLOCKS); }
+
+// ---- what the pcg solve takes from here (bsm_internal.hpp) -------------------
+namespace {
+template <typename TA, typename TF>
+int first_iterate_t(const bsm_nd_factor* f, const bsm_sym* S, int64_t n, int64_t k, const void* b_dev, double* B,
+                    double* X, double* R, TF* W, ull* part, RefineCol* st, unsigned* nb, hipStream_t s) {
+    const unsigned eb = blocks_for((uint64_t)n * (uint64_t)k, 256);
+    const unsigned lb = blocks_for((uint64_t)n, 256, REFINE_MAX_BLOCKS);
+    refine_load<TA><<<lb, 256, 0, s>>>(n, k, static_cast<const TA*>(b_dev), B, part);
+    BSM_HIP_TRY(hipGetLastError());
+    refine_begin<<<1, 256, 0, s>>>((int)lb, k, part, st);
+    BSM_HIP_TRY(hipGetLastError());
+    refine_scale_cast<TF><<<eb, 256, 0, s>>>(n, k, B, st, W);
+    BSM_HIP_TRY(hipGetLastError());
+    BSM_TRY(nd_factor_solve(f, BSM_ND_SYS_A, (uint64_t)k, (uint64_t)n, W, W, s));
+    refine_update<TF><<<eb, 256, 0, s>>>(n, k, W, st, X, nullptr, true);
+    BSM_HIP_TRY(hipGetLastError());
+    return resid_launch<TA>(n, k, S, X, B, R, part, nb, s);
+}
+}  // namespace
+
+int refine_first_iterate(const bsm_nd_factor* f, const bsm_csr* a, const bsm_sym* S, int64_t n, int64_t k,
+                         const void* b_dev, double* B, double* X, double* R, void* W, ull* part, RefineCol* st,
+                         unsigned* nb, hipStream_t s) {
+    if (a->dtype == BSM_F64)
+        return f->dtype == BSM_F64
+                   ? first_iterate_t<double, double>(f, S, n, k, b_dev, B, X, R, static_cast<double*>(W), part, st, nb, s)
+                   : first_iterate_t<double, float>(f, S, n, k, b_dev, B, X, R, static_cast<float*>(W), part, st, nb, s);
+    return f->dtype == BSM_F64
+               ? first_iterate_t<float, double>(f, S, n, k, b_dev, B, X, R, static_cast<double*>(W), part, st, nb, s)
+               : first_iterate_t<float, float>(f, S, n, k, b_dev, B, X, R, static_cast<float*>(W), part, st, nb, s);
+}
+
+int refine_precondition(const bsm_nd_factor* f, int64_t n, int64_t k, const double* V, const RefineCol* st, void* W,
+                        hipStream_t s) {
+    const unsigned eb = blocks_for((uint64_t)n * (uint64_t)k, 256);
+    if (f->dtype == BSM_F64) refine_scale_cast<double><<<eb, 256, 0, s>>>(n, k, V, st, static_cast<double*>(W));
+    else refine_scale_cast<float><<<eb, 256, 0, s>>>(n, k, V, st, static_cast<float*>(W));
+    BSM_HIP_TRY(hipGetLastError());
+    return nd_factor_solve(f, BSM_ND_SYS_A, (uint64_t)k, (uint64_t)n, W, W, s);
+}
+
+int refine_residual(const bsm_csr* a, const bsm_sym* S, int64_t n, int64_t k, const double* X, const double* B,
+                    double* R, ull* part, unsigned* nb, hipStream_t s) {
+    return a->dtype == BSM_F64 ? resid_launch<double>(n, k, S, X, B, R, part, nb, s)
+                               : resid_launch<float>(n, k, S, X, B, R, part, nb, s);
+}
 
 int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s) {
     if (n == 0) return BSM_OK;

@@ -241,6 +241,47 @@ def nd_factor_solve_refined(factor, a, b: torch.Tensor, out: torch.Tensor | None
     return out, RefineInfo(iters, berr, berr <= tol_used, tol_used)
 
 
+def nd_factor_solve_pcg(factor, a, b: torch.Tensor, out: torch.Tensor | None = None, *, max_iter: int = 50,
+                        tol: float | None = None, stream=None):
+    """``NdFactor.solve_pcg`` with ``b`` and ``x`` resident in HBM
+    (``bsm_dev_nd_factor_solve_pcg``). The arguments are
+    ``nd_factor_solve_refined``'s. Returns ``(out, PcgInfo)``. Runs on
+    ``stream`` and is synchronous for it; the same kernels and bits as the
+    host-buffer call."""
+    from .solver import PcgInfo, check_refine_args, refine_tol_in_use
+    from .sparse import _raise_for
+    from .util import MatErr, MatErrKind
+
+    h = factor._h()
+    if b.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"nd_factor_solve_pcg: b is {b.dtype}, needs float32 or float64")
+    b_np = np.dtype(np.float64) if b.dtype == torch.float64 else np.dtype(np.float32)
+    check_refine_args(a, b_np, max_iter, tol, "nd_factor_solve_pcg")
+    out = torch.empty_like(b) if out is None else out
+    for name, t in (("b", b), ("out", out)):
+        if t.dtype != b.dtype:
+            raise TypeError(f"nd_factor_solve_pcg: {name} is {t.dtype}, a is {a.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"nd_factor_solve_pcg: {name} is not on the device")
+        if t.dim() not in (1, 2) or not t.is_contiguous():
+            raise ValueError(f"nd_factor_solve_pcg: {name} must be contiguous, (n,) or (n, k), got {tuple(t.shape)}")
+    if out.shape != b.shape or out.device != b.device:
+        raise ValueError(f"nd_factor_solve_pcg: out is {tuple(out.shape)} on {out.device}, b {tuple(b.shape)} "
+                         f"on {b.device}")
+    if a.dims.rows != factor.n or a.dims.cols != factor.n or b.shape[0] != factor.n:
+        raise MatErr(MatErrKind.IncorrectDimensions)
+    k = b.shape[1] if b.dim() == 2 else 1
+    iters = np.zeros(k, dtype=np.uint32)
+    berr = np.zeros(k, dtype=np.float64)
+    flags = np.zeros(k, dtype=np.uint32)
+    dev = a._device()
+    tol_used = refine_tol_in_use(a, dev, tol)
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_solve_pcg(
+        h, dev.handle, k, _p(b), _p(out), max_iter, tol_used, _lib.ptr(iters), _lib.ptr(berr), _lib.ptr(flags),
+        _stream(stream)))
+    return out, PcgInfo(iters, berr, berr <= tol_used, (flags & 1) != 0, tol_used)
+
+
 def nd_factor_inv_diag(factor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
     """``diag(A^-1)`` of a kept factor (``solver.NdFactor.inv_diag``) into a
     device tensor (``bsm_dev_nd_factor_inv_diag``): ``(n,)``, contiguous, of

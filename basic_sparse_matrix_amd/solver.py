@@ -108,6 +108,20 @@ class RefineInfo:
     tol: float
 
 
+@dataclass
+class PcgInfo:
+    """What a pcg solve reports per right-hand column: the CG steps made, the
+    backward error of the returned ``x`` (of its true residual), whether it
+    is at or below ``tol``, whether the column broke down (``S`` or the
+    factor not positive definite), and the ``tol`` that was used."""
+
+    iters: np.ndarray  # uint32 [k]
+    berr: np.ndarray  # float64 [k]
+    converged: np.ndarray  # bool [k]
+    breakdown: np.ndarray  # bool [k]
+    tol: float
+
+
 def refine_default_tol(a: Csr) -> float:
     """``(m + 2) 2^-53`` with ``m`` the longest row of ``a``'s lower triangle
     mirrored: the rounding bound of the f64 residual itself, the library's
@@ -149,7 +163,8 @@ class NdFactor:
     place (``device.nd_factor_solve`` solves on device tensors), and read the
     selected inverse (``inv_diag()``, ``inv_entries()``, ``inv_on()``:
     ``A^-1`` on the pattern of ``L + L^T``). ``solve_refined`` refines a
-    solve with f64 residuals and reports its backward error; the factor's
+    solve with f64 residuals and reports its backward error, ``solve_pcg``
+    uses the factor as the preconditioner of conjugate gradients; the factor's
     dtype may be chosen apart from the matrix's
     (``cholesky_nd(a, factor_dtype=...)``). The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
@@ -232,6 +247,41 @@ class NdFactor:
                                                    _lib.ptr_array(out.data), max_iter, tol_used, _lib.ptr(iters),
                                                    _lib.ptr(berr)))
         return out, RefineInfo(iters, berr, berr <= tol_used, tol_used)
+
+    def solve_pcg(self, a: Csr, b: Dense, *, max_iter: int = 50, tol: float | None = None):
+        """Preconditioned conjugate gradients on this factor
+        (``bsm_nd_factor_solve_pcg``): ``S x = b`` with the factor's solve as
+        preconditioner, each column its own CG, everything but that solve in
+        f64. ``a``, ``b`` and ``tol`` are ``solve_refined``'s, and so is the
+        first iterate; where refinement needs ``a`` close to the factored
+        matrix, this converges for any positive definite ``a`` (a stale
+        factor, ``3 A``, a low-rank change) in at most ``max_iter`` steps.
+        Returns ``(x, PcgInfo)``: ``berr`` is the backward error of ``x``'s
+        true residual, ``breakdown`` marks a column on which ``a`` or the
+        factor proved not positive definite (its ``x`` is that of its last
+        completed step)."""
+        h = self._h()
+        dims = b.get_dims()
+        n, k = dims.rows, dims.cols
+        check_refine_args(a, b.dtype if k else a.dtype, max_iter, tol, "NdFactor.solve_pcg")
+        if a.dims.rows != self.n or a.dims.cols != self.n or n != self.n:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        b_cols = []
+        for j in range(k):
+            c = np.ascontiguousarray(b.get_col(j))
+            if c.shape[0] < n:
+                raise Panic(f"index out of bounds: the len is {c.shape[0]} but the index is {c.shape[0]}")
+            b_cols.append(np.ascontiguousarray(c[:n]))
+        dev = a._device()
+        tol_used = refine_tol_in_use(a, dev, tol)
+        lib = _lib.require_device()
+        out = Dense.new_default_with_dims(k, n, dtype=a.dtype)
+        iters = np.zeros(k, dtype=np.uint32)
+        berr = np.zeros(k, dtype=np.float64)
+        flags = np.zeros(k, dtype=np.uint32)
+        _raise_for(lib.bsm_nd_factor_solve_pcg(h, dev.handle, k, n, _lib.ptr_array(b_cols), _lib.ptr_array(out.data),
+                                               max_iter, tol_used, _lib.ptr(iters), _lib.ptr(berr), _lib.ptr(flags)))
+        return out, PcgInfo(iters, berr, berr <= tol_used, (flags & 1) != 0, tol_used)
 
     def refactor(self, a: Csr) -> None:
         """New values on the same pattern (``bsm_nd_factor_refactor``): the

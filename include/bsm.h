@@ -362,6 +362,39 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *  - bsm_dev_nd_factor_solve_refined: the same with b and x in HBM on the
  *    factor's device, ROW-major n x k of a's dtype (x may be b), on `stream`;
  *    synchronous for that stream. The same kernels and bits as the host call.
+ *  - bsm_nd_factor_solve_pcg: preconditioned conjugate gradients on the kept
+ *    factor, for the systems refinement cannot do: S x = b as above with M^-1
+ *    the factor's solve as preconditioner, each of the k columns its own CG.
+ *    It converges for any positive definite S and M (a stale factor, the
+ *    factor of a scaled or low-rank-changed matrix), where the refined solve
+ *    needs rho(I - M^-1 S) < 1. Arguments as bsm_nd_factor_solve_refined's;
+ *    everything but M^-1 is f64 for both dtypes of a. x_0 = M^-1 b is the
+ *    refined solve's first iterate (max_iter == 0 gives the bits of
+ *    bsm_nd_factor_solve_refined with max_iter == 0 in x and berr). Then at
+ *    most max_iter steps (50 is the usual choice): q = S p, alpha = rho /
+ *    (p . q), x += alpha p, r -= alpha q, z = M^-1 r (r scaled by a power of
+ *    two into [1, 2) and cast to the factor's dtype), beta = -alpha (q . z) /
+ *    rho (the flexible form: an M^-1 rounded to f32 and rescaled per step is
+ *    not one linear operator), rho = r . z, p = z + beta p. omega_j of the
+ *    recurrence's r is computed after every step; at or below tol the true
+ *    residual b - S x is formed: at or below tol too the column has
+ *    converged, otherwise it takes the true residual for r and goes on with
+ *    beta = 0 (a restart). iters[j] counts the steps, berr[j] is the omega of
+ *    the TRUE residual of the returned x_j, tol and its default are the
+ *    refined solve's. flags (uint32 [k] or NULL): bit 0 set where the column
+ *    broke down -- p . q or r . z was <= 0 or not finite, so S or the factor
+ *    is not positive definite -- and stopped with the x of its last completed
+ *    step. A non-finite omega stops its column; b_j == 0 gives x_j = 0, berr
+ *    0, iters 0. BSM_OK in all these cases: berr[j] <= tol says whether
+ *    column j converged. Column j's x, iters, berr and flags depend neither
+ *    on k nor on the other columns, and the same call gives the same bits
+ *    (sums of a fixed number of partials in a fixed order, no floating-point
+ *    atomics). Errors and their codes are bsm_nd_factor_solve_refined's, all
+ *    before any device work and with every output untouched. Temporaries: six
+ *    f64 n x k arrays and one of the factor's dtype.
+ *  - bsm_dev_nd_factor_solve_pcg: the same with b and x in HBM on the
+ *    factor's device, ROW-major n x k of a's dtype (x may be b), on `stream`;
+ *    synchronous for that stream. The same kernels and bits as the host call.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -388,6 +421,12 @@ int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64
                                 uint32_t* iters, double* berr);
 int bsm_dev_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
                                     uint32_t max_iter, double tol, uint32_t* iters, double* berr, void* stream);
+int bsm_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                            const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
+                            uint32_t* iters, double* berr, uint32_t* flags);
+int bsm_dev_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
+                                uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags,
+                                void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

@@ -764,6 +764,20 @@ struct Refined {
     double tol = 0.0;
 };
 
+/// What NdFactor::solve_pcg returns: x, and per right-hand column the CG steps
+/// made, the backward error of x's true residual, whether it is at or below
+/// tol, whether the column broke down (S or the factor not positive definite:
+/// x is that of its last completed step), and the tol in use.
+template <class T>
+struct Pcg {
+    Dense<T> x;
+    std::vector<uint32_t> iters;
+    std::vector<double> berr;
+    std::vector<bool> converged;
+    std::vector<bool> breakdown;
+    double tol = 0.0;
+};
+
 namespace detail {
 /// (m + 2) 2^-53, m the longest row of a's lower triangle mirrored: the
 /// library's default tol (the rounding bound of the f64 residual itself).
@@ -888,6 +902,38 @@ public:
         detail::check(bsm_nd_factor_solve_refined(f_.get(), h.get(), k, n, in_cols.data(), out_cols.data(), max_iter,
                                                   out.tol, out.iters.data(), out.berr.data()));
         for (size_t j = 0; j < k; ++j) out.converged[j] = out.berr[j] <= out.tol;
+        return out;
+    }
+
+    /// Preconditioned conjugate gradients on this factor
+    /// (bsm_nd_factor_solve_pcg): S x = b with the factor's solve as
+    /// preconditioner, every column its own CG, everything but that solve in
+    /// f64. Arguments, tol and the first iterate are solve_refined's; it
+    /// converges for any positive definite `a` (a stale factor, 3 A, a
+    /// low-rank change), in at most max_iter steps.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    Pcg<U> solve_pcg(const Csr<U>& a, const Dense<U>& b, unsigned max_iter = 50, double tol = 0) const {
+        const size_t n = b.get_dims().rows, k = b.get_dims().cols;
+        if (!(tol >= 0)) throw std::invalid_argument("NdFactor::solve_pcg: tol must be >= 0 (0 = the default)");
+        if (a.get_dims().rows != n_ || a.get_dims().cols != n_ || n != n_)
+            throw Panic("NdFactor::solve_pcg: IncorrectDimensions");
+        Pcg<U> out{Dense<U>::new_default_with_dims(k, n), std::vector<uint32_t>(k), std::vector<double>(k),
+                   std::vector<bool>(k), std::vector<bool>(k), tol > 0 ? tol : detail::refine_default_tol(a)};
+        std::vector<const void*> in_cols(k);
+        std::vector<void*> out_cols(k);
+        for (size_t j = 0; j < k; ++j) {
+            in_cols[j] = b.get_col(j).data();
+            out_cols[j] = out.x.get_col_mut(j).data();
+        }
+        std::vector<uint32_t> flags(k);
+        auto h = a.device();
+        detail::check(bsm_nd_factor_solve_pcg(f_.get(), h.get(), k, n, in_cols.data(), out_cols.data(), max_iter,
+                                              out.tol, out.iters.data(), out.berr.data(), flags.data()));
+        for (size_t j = 0; j < k; ++j) {
+            out.converged[j] = out.berr[j] <= out.tol;
+            out.breakdown[j] = (flags[j] & 1u) != 0;
+        }
         return out;
     }
 

@@ -305,6 +305,8 @@ def main():
         print(json.dumps(line), flush=True)
         if order == "nd":
             print(json.dumps(nd_factor_line(A, B, args, by_value, line["wall_ms"], x, (n, rp, ci, v))), flush=True)
+            if args.dtype == "f64":  # a third record: pcg on the kept factor (profiles/nd_pcg_c5.jsonl)
+                print(json.dumps(nd_pcg_ops(A, B, max(args.reps, 1), (n, rp, ci, v))), flush=True)
 
 
 def selinv_kernel_split(path, dtype):
@@ -467,6 +469,61 @@ def nd_refine_ops(A, B, reps, f64_nbytes):
         "resid_ms": stage("refine_resid"), "update_ms": stage("refine_update"), "judge_ms": stage("refine_judge"),
         "factor_f32_nbytes": nbytes, "factor_f64_nbytes": f64_nbytes,
     }
+
+
+def nd_pcg_ops(A, B, reps, pattern):
+    """Preconditioned CG on a kept factor against the refined solve, one
+    device-resident column, host wall ms around synchronous calls (medians):
+    the f32 factor of A on A itself, and the f64 factor of A on A + 0.01 I (a
+    stale factor), on 3 A and on A + 1e-6 I (a shift that is small against
+    A's smallest eigenvalue at g = 1000, 2e-5, as 0.01 is at the tests'
+    g = 11). Per case and solver: iters, berr, converged, ms.
+    pcg_stages_ms: the last step's kernels between their stage marks
+    (pcg_dots_p: the two dots, beta and p = z + beta p; pcg_spmv_dot: q = S p
+    with p . q, and alpha; pcg_step_xr: x, r and their norms, and the rule;
+    pcg_verify: the true residual, its rule and the take-over of r), 0 when
+    the stage timer is off or the stage did not run."""
+    import torch
+
+    from basic_sparse_matrix_amd import cholesky_nd, device
+
+    n, rp, ci, v = pattern
+    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
+    diag = rows == ci.astype(np.int64)
+    A_stale = Csr.from_csr_arrays((n, n), rp, ci, v + 0.01 * diag)
+    A_3 = Csr.from_csr_arrays((n, n), rp, ci, 3.0 * v)
+    A_near = Csr.from_csr_arrays((n, n), rp, ci, v + 1e-6 * diag)
+    bd = torch.tensor(np.ascontiguousarray(B.get_col(0)), device="cuda")
+    xd = torch.empty_like(bd)
+    count = max(5 * reps, 10)
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    out = {"metric": "C5 nd factor: pcg against the refined solve, one device column (host wall ms, medians)",
+           "config": {"g": int(round(n ** 0.5)), "rhs": 1, "calls": count}, "cases": {}}
+    cases = (("f32_factor_on_A", np.float32, A), ("f64_factor_on_A_plus_0.01I", np.float64, A_stale),
+             ("f64_factor_on_3A", np.float64, A_3), ("f64_factor_on_A_plus_1e-6I", np.float64, A_near))
+    for name, fdt, S in cases:
+        with cholesky_nd(A, factor_dtype=fdt) as f:
+            device.nd_factor_solve_pcg(f, S, bd, out=xd)  # builds S's symmetric copy, warms the temporaries
+            device.nd_factor_solve_refined(f, S, bd, out=xd, max_iter=30)
+            t_pcg, t_ref, st = [], [], []
+            for _ in range(count):
+                t0 = time.perf_counter()
+                _, pi = device.nd_factor_solve_pcg(f, S, bd, out=xd)
+                t_pcg.append(time.perf_counter() - t0)
+                st.append(_lib.stage_times())
+                t0 = time.perf_counter()
+                _, ri = device.nd_factor_solve_refined(f, S, bd, out=xd, max_iter=30)
+                t_ref.append(time.perf_counter() - t0)
+        stage = lambda k: round(float(np.median([s.get(k, 0.0) for s in st])), 4)  # noqa: E731
+        out["cases"][name] = {
+            "pcg_iters": int(pi.iters[0]), "pcg_berr": float(pi.berr[0]), "pcg_converged": bool(pi.converged[0]),
+            "pcg_breakdown": bool(pi.breakdown[0]), "pcg_ms": med(t_pcg),
+            "pcg_ms_min_max": [round(1e3 * min(t_pcg), 3), round(1e3 * max(t_pcg), 3)],
+            "pcg_stages_ms": {k: stage(k) for k in ("pcg_dots_p", "pcg_spmv_dot", "pcg_step_xr", "pcg_verify")},
+            "refined_iters": int(ri.iters[0]), "refined_berr": float(ri.berr[0]),
+            "refined_converged": bool(ri.converged[0]), "refined_ms": med(t_ref), "tol": pi.tol,
+        }
+    return out
 
 
 def nd_factor_line(A, B, args, by_value, same_handle_wall_ms, x_fused, pattern):
