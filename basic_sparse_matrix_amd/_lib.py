@@ -122,6 +122,9 @@ SIGNATURES = [
     ("bsm_dev_nd_factor_solve_refined", _int, [_vp, _vp, _u64, _vp, _vp, _u32, ctypes.c_double, _vp, _vp, _vp]),
     ("bsm_nd_factor_solve_pcg", _int, [_vp, _vp, _u64, _u64, _pp, _pp, _u32, ctypes.c_double, _vp, _vp, _vp]),
     ("bsm_dev_nd_factor_solve_pcg", _int, [_vp, _vp, _u64, _vp, _vp, _u32, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    ("bsm_nd_factor_eigsh", _int, [_vp, _vp, _u64, _u64, _u64, ctypes.c_double, _u64, _pp, _vp, _pp, _vp, _vp]),
+    ("bsm_dev_nd_factor_eigsh", _int, [_vp, _vp, _u64, _u64, _u64, ctypes.c_double, _u64, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),
@@ -274,12 +277,13 @@ def ptr_array(arrays) -> ctypes.Array:
 class DeviceCsr:
     """Owning wrapper of a bsm_csr* handle (device-resident finalised Csr)."""
 
-    __slots__ = ("handle", "rows", "cols", "nnz", "dtype", "refine_tol")
+    __slots__ = ("handle", "rows", "cols", "nnz", "dtype", "refine_tol", "sym_norm_inf")
 
     def __init__(self, handle: int):
         lib = load()
         self.handle = handle
         self.refine_tol = None  # the refined solve's default tol for this matrix, once computed (solver.py)
+        self.sym_norm_inf = None  # ||S||inf of the mirrored lower triangle, once computed (solver.py)
         r, c, n, d = _u64(), _u64(), _u64(), _int()
         check(lib.bsm_csr_shape(handle, ctypes.byref(r), ctypes.byref(c), ctypes.byref(n), ctypes.byref(d)))
         self.rows, self.cols, self.nnz = r.value, c.value, n.value

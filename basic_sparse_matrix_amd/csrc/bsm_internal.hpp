@@ -461,4 +461,13 @@ int refine_residual(const bsm_csr* a, const bsm_sym* S, int64_t n, int64_t k, co
 // flags: k host entries or null (bit 0: the column broke down).
 int nd_pcg_solve(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b_dev, void* x_dev,
                  uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags, hipStream_t s);
+// The nev smallest eigenpairs of S by block shift-invert Lanczos
+// (kernels_eig.hip); the caller has checked a against f and the arguments
+// (eig_rule.hpp: ncv is the basis size in use, tol >= 0). v0_dev: ROW-major
+// n x block of a's dtype or null; vec_dev: ROW-major n x nev of a's dtype or
+// null; lam / resid: nev host entries; info: 4 host entries or null.
+// Synchronous on s.
+int nd_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv, double tol,
+             uint64_t seed, const void* v0_dev, double* lam, void* vec_dev, double* resid, uint32_t* info,
+             hipStream_t s);
 }  // namespace bsm

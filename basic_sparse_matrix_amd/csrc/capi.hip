@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "bsm_internal.hpp"
+#include "eig_rule.hpp"
 
 namespace bsm {
 
@@ -1190,6 +1191,59 @@ int bsm_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k
         if (berr) berr[j] = be[j];
         if (flags) flags[j] = fl[j];
     }
+    return BSM_OK;
+}
+
+// eigsh's checks, all before any device is asked for; *ncv_use is the basis size in use
+static int eigsh_check(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                       double tol, const double* lam, const double* resid, uint64_t* ncv_use) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle (the factor)");
+    BSM_REQUIRE(a, BSM_ERR_INVALID, "null handle (the matrix)");
+    BSM_REQUIRE(lam && resid, BSM_ERR_INVALID, "null argument (lam or resid)");
+    const EigArg bad = eig_check_args(f->n, nev, block, ncv, tol, ncv_use);
+    BSM_REQUIRE(bad == EIG_ARG_OK, BSM_ERR_INVALID,
+                "eigsh: %s; got nev %llu, block %llu, ncv %llu, tol %g on n = %llu", eig_arg_name(bad),
+                (unsigned long long)nev, (unsigned long long)block, (unsigned long long)ncv, tol,
+                (unsigned long long)f->n);
+    return refine_check(f, a, 0, nullptr, nullptr, tol);  // dtype, device, dimensions
+}
+
+int bsm_dev_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                            double tol, uint64_t seed, const void* v0, double* lam, void* vecs, double* resid,
+                            uint32_t* info, void* stream) {
+    uint64_t m = 0;
+    BSM_TRY(eigsh_check(f, a, nev, block, ncv, tol, lam, resid, &m));
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return nd_eigsh(f, a, nev, block, m, tol, seed, v0, lam, vecs, resid, info, static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                        double tol, uint64_t seed, const void* const* v0_cols, double* lam, void* const* vec_cols,
+                        double* resid, uint32_t* info) {
+    uint64_t m = 0;
+    BSM_TRY(eigsh_check(f, a, nev, block, ncv, tol, lam, resid, &m));
+    const uint64_t n = f->n;
+    for (uint64_t j = 0; j < block && n && v0_cols; ++j)
+        BSM_REQUIRE(v0_cols[j], BSM_ERR_INVALID, "null column pointer %llu (v0)", (unsigned long long)j);
+    for (uint64_t j = 0; j < nev && n && vec_cols; ++j)
+        BSM_REQUIRE(vec_cols[j], BSM_ERR_INVALID, "null column pointer %llu (the vectors)", (unsigned long long)j);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf v0, vec;
+    if (v0_cols && n) BSM_TRY(upload_columns(a->dtype, n, block, v0_cols, v0, s));
+    if (vec_cols && n) BSM_TRY(vec.alloc(n * nev * dtype_size(a->dtype)));
+    std::vector<double> l(nev), r(nev);
+    uint32_t inf[4] = {0, 0, 0, 0};
+    BSM_TRY(nd_eigsh(f, a, nev, block, m, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s));
+    if (vec.p) BSM_TRY(download_columns(a->dtype, n, nev, vec.p, vec_cols, s));
+    for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
+        lam[i] = l[i];
+        resid[i] = r[i];
+    }
+    for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
     return BSM_OK;
 }
 

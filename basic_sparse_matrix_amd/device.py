@@ -282,6 +282,49 @@ def nd_factor_solve_pcg(factor, a, b: torch.Tensor, out: torch.Tensor | None = N
     return out, PcgInfo(iters, berr, berr <= tol_used, (flags & 1) != 0, tol_used)
 
 
+def nd_factor_eigsh(factor, a, nev: int, block: int = 4, ncv: int | None = None, tol: float | None = None,
+                    v0: torch.Tensor | None = None, seed: int = 0, out: torch.Tensor | None = None, *,
+                    vectors: bool = True, stream=None):
+    """``NdFactor.eigsh`` with the start block and the vectors resident in
+    HBM (``bsm_dev_nd_factor_eigsh``). ``v0`` is row-major ``(n, block)`` and
+    ``out`` row-major ``(n, nev)``, contiguous, of ``a``'s dtype, on the
+    factor's device; ``out`` defaults to a new tensor (``None`` is returned
+    with ``vectors=False``). Returns ``(lam, out, EigInfo)`` with ``lam`` a
+    host array. Runs on ``stream`` and is synchronous for it; the same
+    kernels and bits as the host-buffer call."""
+    from .solver import check_eig_args, eig_info
+    from .sparse import _raise_for
+
+    h = factor._h()
+    n = factor.n
+    m, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "nd_factor_eigsh")
+    want = TORCH_DT[np.dtype(a.dtype)]
+    if n == 0:
+        nev = 0
+    if vectors and out is None:
+        out = torch.empty((n, nev), dtype=want, device="cuda")
+    if not vectors:
+        out = None
+    for name, t, shape in (("v0", v0, (n, block)), ("out", out, (n, nev))):
+        if t is None:
+            continue
+        if t.dtype != want:
+            raise TypeError(f"nd_factor_eigsh: {name} is {t.dtype}, a is {a.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"nd_factor_eigsh: {name} is not on the device")
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"nd_factor_eigsh: {name} must be contiguous, {shape}, got {tuple(t.shape)}")
+    lam = np.zeros(nev, dtype=np.float64)
+    resid = np.zeros(nev, dtype=np.float64)
+    info = np.zeros(4, dtype=np.uint32)
+    dev = a._device()
+    if n:
+        _raise_for(_lib.require_device().bsm_dev_nd_factor_eigsh(
+            h, dev.handle, nev, block, m, tol_used, seed, _p(v0) if v0 is not None else None, _lib.ptr(lam),
+            _p(out) if out is not None else None, _lib.ptr(resid), _lib.ptr(info), _stream(stream)))
+    return lam, out, eig_info(a, dev, lam, resid, info, tol_used)
+
+
 def nd_factor_inv_diag(factor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
     """``diag(A^-1)`` of a kept factor (``solver.NdFactor.inv_diag``) into a
     device tensor (``bsm_dev_nd_factor_inv_diag``): ``(n,)``, contiguous, of

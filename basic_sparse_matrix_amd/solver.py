@@ -122,6 +122,25 @@ class PcgInfo:
     tol: float
 
 
+@dataclass
+class EigInfo:
+    """What ``eigsh`` reports: the Lanczos steps made, the basis columns used,
+    the true residuals ``||S y - lam y||2 / ||y||2`` per pair, which pairs
+    have converged (a finite ``lam`` whose true residual is within ``2 tol
+    ||S||inf``, the bound a pair with ``est <= tol`` meets with a factor of
+    two for rounding), whether the block lost rank (the Krylov space is
+    invariant), whether a solve ended above the refined solve's ``tol``, and
+    the ``tol`` that was used."""
+
+    steps: int
+    ncv_used: int
+    resid: np.ndarray  # float64 [nev]
+    converged: np.ndarray  # bool [nev]
+    exhausted: bool
+    inexact: bool
+    tol: float
+
+
 def refine_default_tol(a: Csr) -> float:
     """``(m + 2) 2^-53`` with ``m`` the longest row of ``a``'s lower triangle
     mirrored: the rounding bound of the f64 residual itself, the library's
@@ -144,6 +163,59 @@ def check_refine_args(a: Csr, b_dtype, max_iter, tol, what: str) -> None:
         raise ValueError(f"{what}: max_iter must be an integer >= 0, got {max_iter!r}")
     if tol is not None and not tol > 0:  # a NaN is refused here too
         raise ValueError(f"{what}: tol must be > 0 (None = the default), got {tol!r}")
+
+
+def sym_norm_inf(a: Csr, dev=None) -> float:
+    """``||S||inf`` of ``a``'s lower triangle mirrored, computed once per
+    device handle when one is given."""
+    if dev is not None and dev.sym_norm_inf is not None:
+        return dev.sym_norm_inf
+    rp, ci, v = a._csr_arrays()
+    n = a.dims.rows
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp.astype(np.int64)))
+    cols = ci.astype(np.int64)
+    av = np.abs(np.asarray(v, dtype=np.float64))
+    low, strict = cols <= rows, cols < rows
+    sums = np.bincount(rows[low], weights=av[low], minlength=n) + np.bincount(cols[strict], weights=av[strict],
+                                                                               minlength=n)
+    out = float(sums.max()) if n else 0.0
+    if dev is not None:
+        dev.sym_norm_inf = out
+    return out
+
+
+EIG_MAX_BLOCK = 32
+EIG_DEFAULT_NCV = 128
+
+
+def check_eig_args(a: Csr, n: int, nev, block, ncv, tol, seed, what: str) -> tuple[int, float]:
+    """The host-side checks ``eigsh`` and ``device.nd_factor_eigsh`` share;
+    returns the basis size and the ``tol`` in use."""
+    if a.dtype not in _FLOATS:
+        raise TypeError(f"{what}: needs Csr<f32> (or f64), got {a.dtype}")
+    if a.dims.rows != n or a.dims.cols != n:
+        raise MatErr(MatErrKind.IncorrectDimensions)
+    if int(nev) != nev or nev < 1:
+        raise ValueError(f"{what}: nev must be an integer >= 1, got {nev!r}")
+    if int(block) != block or not 1 <= block <= EIG_MAX_BLOCK:
+        raise ValueError(f"{what}: block must be an integer in 1..{EIG_MAX_BLOCK}, got {block!r}")
+    if ncv is not None and (int(ncv) != ncv or ncv < 1):
+        raise ValueError(f"{what}: ncv must be an integer >= 1 (None = min(n, {EIG_DEFAULT_NCV})), got {ncv!r}")
+    if tol is not None and not tol > 0:  # a NaN is refused here too
+        raise ValueError(f"{what}: tol must be > 0 (None = the default), got {tol!r}")
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed must be an integer in 0..2^64-1, got {seed!r}")
+    m = (min(n, EIG_DEFAULT_NCV) if ncv is None else int(ncv)) // int(block) * int(block)
+    if n and not nev <= m <= n:
+        raise ValueError(f"{what}: ncv (rounded down to a multiple of block: {m}) must be in nev..n = {nev}..{n}")
+    return m, float(tol) if tol is not None else (2.0 ** -26 if a.dtype == np.float64 else 2.0 ** -12)
+
+
+def eig_info(a: Csr, dev, lam, resid, info, tol_used) -> EigInfo:
+    bound = 2.0 * tol_used * sym_norm_inf(a, dev)
+    with np.errstate(invalid="ignore"):
+        conv = np.isfinite(lam) & (resid <= bound)
+    return EigInfo(int(info[0]), int(info[1]), resid, conv, bool(info[3] & 1), bool(info[3] & 2), tol_used)
 
 
 def refine_tol_in_use(a: Csr, dev, tol) -> float:
@@ -282,6 +354,56 @@ class NdFactor:
         _raise_for(lib.bsm_nd_factor_solve_pcg(h, dev.handle, k, n, _lib.ptr_array(b_cols), _lib.ptr_array(out.data),
                                                max_iter, tol_used, _lib.ptr(iters), _lib.ptr(berr), _lib.ptr(flags)))
         return out, PcgInfo(iters, berr, berr <= tol_used, (flags & 1) != 0, tol_used)
+
+    def eigsh(self, a: Csr, nev: int, block: int = 4, ncv: int | None = None, tol: float | None = None,
+              v0: Dense | None = None, seed: int = 0, *, vectors: bool = True):
+        """The ``nev`` smallest eigenvalues of ``S`` (``a``'s lower triangle
+        mirrored, as ``solve_refined`` defines it) and their eigenvectors, by
+        block shift-invert Lanczos on this factor (``bsm_nd_factor_eigsh``):
+        the operator is ``A^-1`` by the refined solve, ``block`` columns at a
+        time, with full reorthogonalisation, in a basis of at most ``ncv``
+        columns (rounded down to a multiple of ``block``; ``None``:
+        ``min(n, 128)``). ``tol`` bounds the residual estimate of a Ritz pair
+        (``None``: ``2^-26`` for an f64 ``a``, ``2^-12`` for an f32 one);
+        ``v0`` is a start block (a ``Dense`` of ``a``'s dtype, ``n x block``),
+        else it is generated from ``seed``. Returns ``(lam, Dense, EigInfo)``:
+        ``lam`` ascending (f64), the unit eigenvectors as the columns of a
+        ``Dense`` of ``a``'s dtype (``None`` with ``vectors=False``). Pairs
+        that the basis could not give (an ``exhausted`` run) have ``lam`` NaN.
+        There is no restart: call again with ``v0`` made of the first
+        ``block`` vectors and a larger ``ncv``. An eigenvalue of multiplicity
+        above ``block`` is found ``block`` times at most (a long run may pick
+        up a further copy from rounding; do not count on it)."""
+        h = self._h()
+        n = self.n
+        m, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "NdFactor.eigsh")
+        v0_cols = None
+        if v0 is not None:
+            dims = v0.get_dims()
+            if v0.dtype != a.dtype:
+                raise TypeError(f"NdFactor.eigsh: v0 must have a's dtype {a.dtype}, got {v0.dtype}")
+            if dims.rows != n or dims.cols != block:
+                raise MatErr(MatErrKind.IncorrectDimensions)
+            v0_cols = []
+            for j in range(block):
+                c = np.ascontiguousarray(v0.get_col(j))
+                if c.shape[0] < n:
+                    raise Panic(f"index out of bounds: the len is {c.shape[0]} but the index is {c.shape[0]}")
+                v0_cols.append(np.ascontiguousarray(c[:n]))
+        if n == 0:
+            nev = 0
+        lam = np.zeros(nev, dtype=np.float64)
+        resid = np.zeros(nev, dtype=np.float64)
+        info = np.zeros(4, dtype=np.uint32)
+        out = Dense.new_default_with_dims(nev, n, dtype=a.dtype) if vectors else None
+        dev = a._device()
+        if n:
+            lib = _lib.require_device()
+            _raise_for(lib.bsm_nd_factor_eigsh(h, dev.handle, nev, block, m, tol_used, seed,
+                                               _lib.ptr_array(v0_cols) if v0_cols is not None else None,
+                                               _lib.ptr(lam), _lib.ptr_array(out.data) if vectors else None,
+                                               _lib.ptr(resid), _lib.ptr(info)))
+        return lam, out, eig_info(a, dev, lam, resid, info, tol_used)
 
     def refactor(self, a: Csr) -> None:
         """New values on the same pattern (``bsm_nd_factor_refactor``): the

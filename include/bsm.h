@@ -395,6 +395,61 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *  - bsm_dev_nd_factor_solve_pcg: the same with b and x in HBM on the
  *    factor's device, ROW-major n x k of a's dtype (x may be b), on `stream`;
  *    synchronous for that stream. The same kernels and bits as the host call.
+ *  - bsm_nd_factor_eigsh: the nev smallest eigenvalues of S (as above: a's
+ *    lower triangle mirrored) and their eigenvectors, by block shift-invert
+ *    Lanczos at sigma = 0: the operator is A^-1, which the factor makes cheap,
+ *    and its largest eigenvalues theta are the wanted 1 / lambda. The basis is
+ *    kept as blocks V_0, V_1, ... of `block` columns (1..32), at most ncv
+ *    columns (rounded down to a multiple of block; 0: min(n, 128)). V_0 is
+ *    v0_cols (block host columns of a's dtype) or, for NULL, bsm_hash(seed,
+ *    row, column, 6) through bsm_unit_uniform mapped to [-1, 1) and rounded to
+ *    a's dtype, orthonormalised like every later block. A step is W = A^-1
+ *    V_j by bsm_nd_factor_solve_refined's loop (max_iter 5, its default tol,
+ *    the block passed in a's dtype: f64 backward error for an f64 a whichever
+ *    dtype the factor has, f32 operator accuracy for an f32 a); classical
+ *    Gram-Schmidt twice against every block so far (C = V^T W, W -= V C; A_j
+ *    is the symmetrised block of the summed C that belongs to V_j); Cholesky-
+ *    QR twice (W^T W = R1^T R1, W = W R1^-1, again with R2; V_{j+1} = W,
+ *    B_{j+1} = R2 R1). A pivot of the first Cholesky <= 2^-50 times the
+ *    column's squared norm before the projections means the block has lost
+ *    rank: the Krylov space is invariant, the run stops (info flag bit 0,
+ *    "exhausted") and returns the pairs of the basis so far, fewer than nev
+ *    where the basis is smaller (lam and resid NaN, vectors 0 for the rest).
+ *    The host solves T s = theta s for the block-tridiagonal T of the A_j
+ *    and B_j (cyclic Jacobi, no LAPACK) after every step that has nev
+ *    columns; est_i = ||B_{j+1} s_i[last block rows]||2 / |theta_i|, and the
+ *    run stops when the nev largest theta all have est <= tol, or at ncv.
+ *    tol == 0: 2^-26 for an f64 a, 2^-12 for an f32 a (the square root of the
+ *    unit roundoff: the eigenvalue error is quadratic in the residual, so the
+ *    values are good to the roundoff over the relative gap; pass a smaller
+ *    tol for sharper vectors). Results: lam[nev] ascending, vec_cols (nev host
+ *    columns of a's dtype, or NULL for values only) of unit 2-norm without a
+ *    sign convention, resid[i] = ||S y_i - lam_i y_i||2 / ||y_i||2 formed anew
+ *    in f64 from the f64 vectors; since S y - lam y = -lam S (A^-1 y - theta
+ *    y), a pair with est <= tol has resid <= tol ||S||inf up to rounding.
+ *    info (uint32 [4] or NULL): the steps, the basis columns used, the pairs
+ *    with est <= tol, flags (bit 0 exhausted; bit 1 "inexact": a solve's
+ *    backward error ended above the refined solve's tol, and the run went
+ *    on). BSM_OK whether or not the pairs converged: info and resid say. There
+ *    is no restart: call again with v0 = the first `block` vectors returned
+ *    and a larger ncv. An eigenvalue of multiplicity above `block` is found
+ *    `block` times at most (in exact arithmetic: a run that goes on long after
+ *    those copies have converged may pick up a further one from rounding; do
+ *    not count on it). The same call gives the same bits (per-workgroup
+ *    partials whose number and order depend on n and block alone, or on S,
+ *    added in index order; no floating-point atomics). Errors, all before any
+ *    device work and with every output untouched: a null f, a, lam or resid ->
+ *    BSM_ERR_INVALID ("null ..."); tol < 0 or NaN, nev < 1, block outside
+ *    1..32, ncv (after rounding) < nev or > n -> BSM_ERR_INVALID naming the
+ *    argument; dtype, device, dimensions and a handle without values as
+ *    bsm_nd_factor_solve_refined. n == 0 is accepted with nev == 0. An ncv
+ *    above 8192 -> BSM_ERR_UNSUPPORTED (T is dense on the host).
+ *    Temporaries: (ncv + 3 block) n f64 and the partials, plus the refined
+ *    solve's for `block` columns.
+ *  - bsm_dev_nd_factor_eigsh: the same with v0 and the vectors in HBM on the
+ *    factor's device, ROW-major n x block and n x nev of a's dtype (either may
+ *    be NULL), on `stream`; synchronous for that stream. The same kernels and
+ *    bits as the host call.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -427,6 +482,12 @@ int bsm_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k
 int bsm_dev_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
                                 uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags,
                                 void* stream);
+int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                        double tol, uint64_t seed, const void* const* v0_cols, double* lam, void* const* vec_cols,
+                        double* resid, uint32_t* info);
+int bsm_dev_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                            double tol, uint64_t seed, const void* v0, double* lam, void* vecs, double* resid,
+                            uint32_t* info, void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

@@ -778,6 +778,25 @@ struct Pcg {
     double tol = 0.0;
 };
 
+/// What NdFactor::eigsh returns: lam ascending, the unit eigenvectors as the
+/// columns of `vectors`, the true residuals ||S y - lam y||2 / ||y||2, the
+/// Lanczos steps, the basis columns used, the number of pairs whose residual
+/// estimate is at or below tol, whether the block lost rank (the Krylov space
+/// is invariant: pairs the basis could not give have lam NaN), whether a solve
+/// ended above the refined solve's tol, and the tol in use.
+template <class T>
+struct Eig {
+    std::vector<double> lam;
+    Dense<T> vectors;
+    std::vector<double> resid;
+    uint32_t steps = 0;
+    uint32_t ncv_used = 0;
+    uint32_t converged = 0;
+    bool exhausted = false;
+    bool inexact = false;
+    double tol = 0.0;
+};
+
 namespace detail {
 /// (m + 2) 2^-53, m the longest row of a's lower triangle mirrored: the
 /// library's default tol (the rounding bound of the f64 residual itself).
@@ -934,6 +953,43 @@ public:
             out.converged[j] = out.berr[j] <= out.tol;
             out.breakdown[j] = (flags[j] & 1u) != 0;
         }
+        return out;
+    }
+
+    /// The nev smallest eigenvalues of S (a's lower triangle mirrored) and
+    /// their eigenvectors by block shift-invert Lanczos on this factor
+    /// (bsm_nd_factor_eigsh): A^-1 by the refined solve, `block` columns at a
+    /// time, full reorthogonalisation, at most ncv basis columns (0: min(n,
+    /// 128); rounded down to a multiple of block). tol == 0: 2^-26 for f64,
+    /// 2^-12 for f32. v0: an n x block start block, or null for the one made
+    /// from `seed`. Bad arguments throw as the C call reports them.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    Eig<U> eigsh(const Csr<U>& a, size_t nev, size_t block = 4, size_t ncv = 0, double tol = 0,
+                 const Dense<U>* v0 = nullptr, uint64_t seed = 0) const {
+        if (!(tol >= 0)) throw std::invalid_argument("NdFactor::eigsh: tol must be >= 0 (0 = the default)");
+        if (a.get_dims().rows != n_ || a.get_dims().cols != n_ ||
+            (v0 && (v0->get_dims().rows != n_ || v0->get_dims().cols != block)))
+            throw Panic("NdFactor::eigsh: IncorrectDimensions");
+        if (n_ == 0) nev = 0;
+        Eig<U> out{std::vector<double>(nev), Dense<U>::new_default_with_dims(nev, n_), std::vector<double>(nev)};
+        out.tol = tol > 0 ? tol : (sizeof(U) == 8 ? 0x1p-26 : 0x1p-12);
+        if (n_ == 0) return out;
+        std::vector<const void*> in_cols(v0 ? block : 0);
+        for (size_t j = 0; j < in_cols.size(); ++j) in_cols[j] = v0->get_col(j).data();
+        std::vector<void*> out_cols(nev);
+        for (size_t j = 0; j < nev; ++j) out_cols[j] = out.vectors.get_col_mut(j).data();
+        uint32_t info[4] = {0, 0, 0, 0};
+        double none = 0.0;  // nev == 0 is refused by the library, not by a null pointer here
+        auto h = a.device();
+        detail::check(bsm_nd_factor_eigsh(f_.get(), h.get(), nev, block, ncv, out.tol, seed,
+                                          v0 ? in_cols.data() : nullptr, nev ? out.lam.data() : &none,
+                                          out_cols.data(), nev ? out.resid.data() : &none, info));
+        out.steps = info[0];
+        out.ncv_used = info[1];
+        out.converged = info[2];
+        out.exhausted = (info[3] & 1u) != 0;
+        out.inexact = (info[3] & 2u) != 0;
         return out;
     }
 

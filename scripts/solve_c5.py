@@ -166,6 +166,9 @@ def main():
     ap.add_argument("--kernel-stats", default=None,
                     help="a rocprofv3 kernel-stats CSV of an earlier run of this command: the nd factor line then "
                          "carries the selected inverse's device time per kernel and call (selinv_kernels_ms)")
+    ap.add_argument("--eig", type=int, default=0, metavar="NEV",
+                    help="only the eigsh record: the NEV smallest eigenpairs on the kept factor, f64 and f32 factor, "
+                         "block 4 and 8 (profiles/nd_eig_c5.jsonl)")
     args = ap.parse_args()
     dt = np.float64 if args.dtype == "f64" else np.float32
     g = args.g
@@ -173,6 +176,10 @@ def main():
     rp, ci, v, b, x_true = system(g, dt)
     A = Csr.from_csr_arrays((n, n), rp, ci, v)
     B = Dense.from_columns([b])
+    if args.eig:
+        _lib.stage_timing(True)
+        print(json.dumps(nd_eig_ops(A, B, args.eig, max(args.reps, 1), g)), flush=True)
+        return
     fixture = None
     fx_path = os.path.join(ROOT, "tests", "golden", f"c5_poisson_{g}.json")
     if os.path.exists(fx_path) and args.dtype == "f64":
@@ -523,6 +530,66 @@ def nd_pcg_ops(A, B, reps, pattern):
             "refined_iters": int(ri.iters[0]), "refined_berr": float(ri.berr[0]),
             "refined_converged": bool(ri.converged[0]), "refined_ms": med(t_ref), "tol": pi.tol,
         }
+    return out
+
+
+def nd_eig_ops(A, B, nev, reps, g):
+    """The nev smallest eigenpairs of the f64 system by NdFactor.eigsh (block
+    shift-invert Lanczos), f64 and f32 factor, block 4 and 8, vectors left on
+    the device; host wall ms around synchronous calls (medians of `reps`).
+    Per case: steps, basis columns, wall ms, resid, the error of each lam
+    against 4 - 2 cos(p pi / (g + 1)) - 2 cos(q pi / (g + 1)), and
+    last_step_stages_ms: the LAST step's kernels between their stage marks
+    (the stage list restarts with every solve: eig_solve is only the cast
+    after the refined solve, whose own stages precede it; eig_reorth: both
+    Gram-Schmidt passes against all ncv_used columns; eig_qr: Cholesky-QR
+    twice; eig_ritz: the host's Ritz check of the largest T, the stream idle
+    meanwhile; eig_resid: Y = V Z and the residuals). solve_share: steps x the
+    median wall ms of a `block`-column device.nd_factor_solve_refined, over
+    wall ms. reorth_GBs: 4 n ncv_used 8 bytes over the last step's eig_reorth."""
+    import torch
+
+    from basic_sparse_matrix_amd import cholesky_nd, device
+
+    n = g * g
+    exact = np.sort((4.0 - 2.0 * np.cos(np.arange(1, 40) * np.pi / (g + 1))[:, None]
+                     - 2.0 * np.cos(np.arange(1, 40) * np.pi / (g + 1))[None, :]).ravel())[:nev]
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    out = {"metric": "C5 nd factor: the smallest eigenpairs by block shift-invert Lanczos (host wall ms, medians)",
+           "config": {"g": g, "nev": nev, "calls": reps, "ncv": 128}, "cases": {}}
+    for fdt in (np.float64, np.float32):
+        with cholesky_nd(A, factor_dtype=fdt) as f:
+            for block in (4, 8):
+                y = torch.empty((n, nev), dtype=torch.float64, device="cuda")
+                bd = torch.ones((n, block), dtype=torch.float64, device="cuda")
+                xd = torch.empty_like(bd)
+                device.nd_factor_eigsh(f, A, nev, block=block, out=y)  # builds S, warms the temporaries
+                device.nd_factor_solve_refined(f, A, bd, out=xd)
+                t_eig, t_ref, st = [], [], []
+                for _ in range(reps):
+                    t0 = time.perf_counter()
+                    lam, _, info = device.nd_factor_eigsh(f, A, nev, block=block, out=y)
+                    t_eig.append(time.perf_counter() - t0)
+                    st.append(_lib.stage_times())
+                    for _ in range(3):
+                        t0 = time.perf_counter()
+                        device.nd_factor_solve_refined(f, A, bd, out=xd)
+                        t_ref.append(time.perf_counter() - t0)
+                stage = lambda k: round(float(np.median([s_.get(k, 0.0) for s_ in st])), 4)  # noqa: E731
+                stages = {k: stage(k) for k in ("eig_solve", "eig_reorth", "eig_qr", "eig_ritz", "eig_resid")}
+                reorth_bytes = 4.0 * n * info.ncv_used * 8
+                out["cases"][f"{np.dtype(fdt).name}_factor_block{block}"] = {
+                    "steps": info.steps, "ncv_used": info.ncv_used, "converged": int(info.converged.sum()),
+                    "exhausted": info.exhausted, "inexact": info.inexact, "tol": info.tol, "eigsh_ms": med(t_eig),
+                    "eigsh_ms_min_max": [round(1e3 * min(t_eig), 3), round(1e3 * max(t_eig), 3)],
+                    "last_step_stages_ms": stages,
+                    "refined_solve_block_cols_ms": med(t_ref),
+                    "solve_share": round(info.steps * float(np.median(t_ref)) / float(np.median(t_eig)), 3),
+                    "reorth_GBs": round(reorth_bytes / (stages["eig_reorth"] * 1e-3) / 1e9, 1)
+                    if stages["eig_reorth"] > 0 else None,
+                    "resid": [float(r) for r in info.resid],
+                    "lam_err_vs_analytic": [float(e) for e in np.abs(lam - exact)],
+                }
     return out
 
 
