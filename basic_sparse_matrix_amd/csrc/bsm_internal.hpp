@@ -470,4 +470,11 @@ int nd_pcg_solve(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const voi
 int nd_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv, double tol,
              uint64_t seed, const void* v0_dev, double* lam, void* vec_dev, double* resid, uint32_t* info,
              hipStream_t s);
+// The same for S y = lambda S_M y, S_M being m's lower triangle mirrored (m:
+// n x n, a's dtype and device, checked by the caller): the loop in the S_M
+// inner product. BSM_ERR_UNSUPPORTED when S_M proves not positive definite,
+// with nothing written.
+int nd_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block, uint64_t ncv,
+                 double tol, uint64_t seed, const void* v0_dev, double* lam, void* vec_dev, double* resid,
+                 uint32_t* info, hipStream_t s);
 }  // namespace bsm

@@ -1247,6 +1247,62 @@ int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, 
     return BSM_OK;
 }
 
+// eigsh_gen's checks: eigsh_check's, then the mass matrix against a
+static int eigsh_gen_check(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
+                           uint64_t ncv, double tol, const double* lam, const double* resid, uint64_t* ncv_use) {
+    BSM_TRY(eigsh_check(f, a, nev, block, ncv, tol, lam, resid, ncv_use));
+    BSM_REQUIRE(m->dtype == BSM_F32 || m->dtype == BSM_F64, BSM_ERR_INVALID, "eigsh: m must be f32 or f64");
+    BSM_REQUIRE(m->dtype == a->dtype, BSM_ERR_INVALID, "eigsh: m's dtype differs from a's");
+    BSM_REQUIRE(m->device == f->device, BSM_ERR_INVALID,
+                "eigsh: device differs (m is on device %d, the factor on %d)", m->device, f->device);
+    BSM_REQUIRE(m->rows == f->n && m->cols == f->n, BSM_ERR_DIMENSIONS,
+                "IncorrectDimensions: m is %llu x %llu, the factor's matrix %llu x %llu", (unsigned long long)m->rows,
+                (unsigned long long)m->cols, (unsigned long long)f->n, (unsigned long long)f->n);
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev,
+                                uint64_t block, uint64_t ncv, double tol, uint64_t seed, const void* v0, double* lam,
+                                void* vecs, double* resid, uint32_t* info, void* stream) {
+    if (!m) return bsm_dev_nd_factor_eigsh(f, a, nev, block, ncv, tol, seed, v0, lam, vecs, resid, info, stream);
+    uint64_t nc = 0;
+    BSM_TRY(eigsh_gen_check(f, a, m, nev, block, ncv, tol, lam, resid, &nc));
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return nd_eigsh_gen(f, a, m, nev, block, nc, tol, seed, v0, lam, vecs, resid, info,
+                        static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
+                            uint64_t ncv, double tol, uint64_t seed, const void* const* v0_cols, double* lam,
+                            void* const* vec_cols, double* resid, uint32_t* info) {
+    if (!m) return bsm_nd_factor_eigsh(f, a, nev, block, ncv, tol, seed, v0_cols, lam, vec_cols, resid, info);
+    uint64_t nc = 0;
+    BSM_TRY(eigsh_gen_check(f, a, m, nev, block, ncv, tol, lam, resid, &nc));
+    const uint64_t n = f->n;
+    for (uint64_t j = 0; j < block && n && v0_cols; ++j)
+        BSM_REQUIRE(v0_cols[j], BSM_ERR_INVALID, "null column pointer %llu (v0)", (unsigned long long)j);
+    for (uint64_t j = 0; j < nev && n && vec_cols; ++j)
+        BSM_REQUIRE(vec_cols[j], BSM_ERR_INVALID, "null column pointer %llu (the vectors)", (unsigned long long)j);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf v0, vec;
+    if (v0_cols && n) BSM_TRY(upload_columns(a->dtype, n, block, v0_cols, v0, s));
+    if (vec_cols && n) BSM_TRY(vec.alloc(n * nev * dtype_size(a->dtype)));
+    std::vector<double> l(nev), r(nev);
+    uint32_t inf[4] = {0, 0, 0, 0};
+    BSM_TRY(nd_eigsh_gen(f, a, m, nev, block, nc, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s));
+    if (vec.p) BSM_TRY(download_columns(a->dtype, n, nev, vec.p, vec_cols, s));
+    for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
+        lam[i] = l[i];
+        resid[i] = r[i];
+    }
+    for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
+    return BSM_OK;
+}
+
 int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* const* b_cols,
                                void* const* x_cols) {
     BSM_REQUIRE(f && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");

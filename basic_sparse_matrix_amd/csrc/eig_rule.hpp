@@ -2,7 +2,8 @@
 // (bsm_nd_factor_eigsh, kernels_eig.hip): the argument checks, the start
 // block's values, the p x p Cholesky of a Gram matrix with its rank rule, the
 // block-tridiagonal matrix T, the symmetric eigen-solver of T (cyclic Jacobi,
-// plain C++), the residual estimate of a Ritz pair and the stop rule.
+// plain C++), the residual estimate of a Ritz pair and the stop rule, and the
+// generalised problem's test of its mass matrix (bsm_nd_factor_eigsh_gen).
 // Header-only and free of device types, as pcg_rule.hpp: a plain C++ program
 // drives the whole loop through it with a dense operator
 // (tests/cpp/eig_rule_test.cpp), the device's one-workgroup judge calls the
@@ -113,6 +114,17 @@ inline void eig_mul_upper(int p, const double* R2, const double* R1, double* B) 
             for (int k = i; k <= j; ++k) v += R2[i * p + k] * R1[k * p + j];
             B[i * p + j] = v;
         }
+}
+
+// ---- the generalised problem's mass matrix ---------------------------------------
+// S y = lambda S_M y (bsm_nd_factor_eigsh_gen) runs the same loop in the S_M
+// inner product, and norm2[c] = w_c^T S_M w_c of a block's p columns is then a
+// squared norm. One that is <= 0 or not finite shows that S_M is not positive
+// definite (a zero column of a caller's start block reads the same).
+inline bool eig_mass_pd(int p, const double* norm2) {
+    for (int c = 0; c < p; ++c)
+        if (!(norm2[c] > 0.0) || !std::isfinite(norm2[c])) return false;
+    return true;
 }
 
 // ---- the symmetric eigen-solver -------------------------------------------------

@@ -15,7 +15,10 @@
 // The per-workgroup partials are added in index order by one workgroup; there
 // are no floating-point atomics, so the same call gives the same bits. One
 // reorthogonalisation step reads V twice per pass: about 4 n m 8 bytes for m
-// basis columns.
+// basis columns. The generalised problem S y = lambda S_M y
+// (bsm_nd_factor_eigsh_gen) is the same loop in the S_M inner product, with
+// kernels and a host loop of its own below (eigsh_gen_t); eigsh_t is not
+// touched by it.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -158,18 +161,20 @@ __global__ __launch_bounds__(256) void eig_sum(int nb, int cnt, const double* __
     }
 }
 
-enum { EIG_SUB = 0, EIG_MUL = 1, EIG_YVZ = 2 };
+enum { EIG_SUB = 0, EIG_MUL = 1, EIG_YVZ = 2, EIG_SUBP = 3 };
 
 // SUB: out = W - sum_b V_b M_b (M = C, m x p), the projections taken off in
 //      basis order; MUL: out = W M (M = U, p x p); YVZ: out = sum_b V_b M_b
 //      (M = Z, m x p). SUB and MUL also give gpart[block][c][d], the
-//      workgroup's share of out^T out. out may be W.
+//      workgroup's share of out^T out. SUBP is SUB without that Gram matrix
+//      (the generalised problem's is out^T S_M out). out may be W.
 template <int MODE>
 __global__ __launch_bounds__(256) void eig_combine(int64_t n, int p, int tr, int64_t rw, int nblk,
                                                    const double* __restrict__ V, const double* W,
                                                    const double* __restrict__ M, double* out,
                                                    double* __restrict__ gpart) {
     __shared__ double At[EIG_TILE], Bt[EIG_TILE], red[256];
+    constexpr bool TAKE_OFF = MODE == EIG_SUB || MODE == EIG_SUBP, GRAM = MODE == EIG_SUB || MODE == EIG_MUL;
     const int E = p * p;
     const int64_t lo = (int64_t)blockIdx.x * rw, hi = min(n, lo + rw);
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -179,7 +184,7 @@ __global__ __launch_bounds__(256) void eig_combine(int64_t n, int p, int tr, int
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int i = threadIdx.x + 256 * u;
-            w[u] = (MODE == EIG_SUB && i < have) ? W[t0 * p + i] : 0.0;
+            w[u] = (TAKE_OFF && i < have) ? W[t0 * p + i] : 0.0;
         }
         if constexpr (MODE == EIG_MUL) {
             load_tile(At, W + t0 * p, have, tr * p);
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void eig_combine(int64_t n, int p, int tr, int
                         const int r = i / p, d = i % p;
                         for (int c = 0; c < p; ++c) {
                             const double v = At[r * p + c];
-                            w[u] = fma(MODE == EIG_SUB ? -v : v, Mb[c * p + d], w[u]);
+                            w[u] = fma(TAKE_OFF ? -v : v, Mb[c * p + d], w[u]);
                         }
                     }
                 }
@@ -216,14 +221,14 @@ __global__ __launch_bounds__(256) void eig_combine(int64_t n, int p, int tr, int
         for (int u = 0; u < 8; ++u) {
             const int i = threadIdx.x + 256 * u;
             if (i < have) out[t0 * p + i] = w[u];
-            if (MODE != EIG_YVZ && i < tr * p) Bt[i] = i < have ? w[u] : 0.0;
+            if (GRAM && i < tr * p) Bt[i] = i < have ? w[u] : 0.0;
         }
-        if constexpr (MODE != EIG_YVZ) {
+        if constexpr (GRAM) {
             __syncthreads();
             tile_products(p, tr, Bt, Bt, red, acc);
         }
     }
-    if constexpr (MODE != EIG_YVZ) {
+    if constexpr (GRAM) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = threadIdx.x + 256 * i;
@@ -528,6 +533,431 @@ int eigsh_t(const bsm_nd_factor* f, const bsm_csr* a, const bsm_sym* S, int64_t 
     return BSM_OK;
 }
 
+// ---- the generalised problem S y = lambda S_M y (bsm_nd_factor_eigsh_gen) ------
+// The same loop in the S_M inner product: the operator A^-1 S_M is self-adjoint
+// in it, the basis is S_M-orthonormal, and Q = S_M W travels beside W:
+//   W = A^-1 (S_M V_j)                        eig_cast, nd_refine_solve
+//   Q = S_M W                                 eig_mass
+//   C = V^T Q, W -= V C; Q = S_M W; twice     eig_vtu, eig_sum, eig_combine<SUBP>, eig_mass
+//   G = W^T Q = R1^T R1, (W, Q) = (W, Q) R1^-1, again    eig_vtu, eig_judge, eig_mul2
+// The pass that ends the step leaves V_{j+1} and S_M V_{j+1}: three products
+// with S_M per step and one for the start block. T, the Ritz solve and the
+// stop rule are eigsh's (EigLoop).
+
+// U = S_M X, X and U n x p row-major f64: eig_resid's lane layout (G lanes per
+// row take the row's entries in stored order, explicit fma, a fixed xor tree)
+template <typename TA, int G, int KC>
+__global__ __launch_bounds__(256) void eig_mass(int64_t n, int64_t p, const int64_t* __restrict__ rp,
+                                                const int32_t* __restrict__ col, const TA* __restrict__ val,
+                                                const double* __restrict__ X, double* __restrict__ U) {
+    constexpr int GROUPS = 256 / G;
+    const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+    for (int64_t j0 = 0; j0 < p; j0 += KC) {
+        for (int64_t row0 = (int64_t)blockIdx.x * GROUPS; row0 < n; row0 += (int64_t)gridDim.x * GROUPS) {
+            const int64_t row = row0 + grp;
+            double acc[KC];
+#pragma unroll
+            for (int c = 0; c < KC; ++c) acc[c] = 0.0;
+            if (row < n) {
+                const int64_t e1 = rp[row + 1];
+                for (int64_t e = rp[row] + lane; e < e1; e += G) {
+                    const double v = (double)val[e];
+                    const double* xp = X + (int64_t)col[e] * p + j0;
+#pragma unroll
+                    for (int c = 0; c < KC; ++c) acc[c] = fma(v, xp[c], acc[c]);
+                }
+            }
+#pragma unroll
+            for (int o = G / 2; o > 0; o >>= 1) {
+#pragma unroll
+                for (int c = 0; c < KC; ++c) acc[c] += __shfl_xor(acc[c], o);
+            }
+            if (lane == 0 && row < n) {
+#pragma unroll
+                for (int c = 0; c < KC; ++c) U[row * p + j0 + c] = acc[c];
+            }
+        }
+    }
+}
+
+template <typename TA, int G>
+int eig_mass_g(unsigned nb, int64_t n, int64_t p, const bsm_sym* SM, const double* X, double* U, hipStream_t s) {
+    const TA* v = static_cast<const TA*>(SM->vals);
+    if (p % 4 == 0) eig_mass<TA, G, 4><<<nb, 256, 0, s>>>(n, p, SM->rp, SM->col, v, X, U);
+    else if (p % 2 == 0) eig_mass<TA, G, 2><<<nb, 256, 0, s>>>(n, p, SM->rp, SM->col, v, X, U);
+    else eig_mass<TA, G, 1><<<nb, 256, 0, s>>>(n, p, SM->rp, SM->col, v, X, U);
+    BSM_HIP_TRY(hipGetLastError());
+    return BSM_OK;
+}
+
+// G from S_M's mean row length and the workgroups from n, as refine_resid's
+template <typename TA>
+int eig_mass_launch(int64_t n, int64_t p, const bsm_sym* SM, const double* X, double* U, hipStream_t s) {
+    const int g = resid_group(SM, n);
+    const unsigned nb = resid_blocks(g, n);
+    switch (g) {
+        case 4: return eig_mass_g<TA, 4>(nb, n, p, SM, X, U, s);
+        case 8: return eig_mass_g<TA, 8>(nb, n, p, SM, X, U, s);
+        case 16: return eig_mass_g<TA, 16>(nb, n, p, SM, X, U, s);
+        default: return eig_mass_g<TA, 64>(nb, n, p, SM, X, U, s);
+    }
+}
+
+// eig_vtw with the second operand apart from the first:
+// part[block][b][c][d] = the workgroup's share of V_b[., c] . U[., d], for the
+// nblk basis blocks and, with_w, for W as one more (W^T U)
+__global__ __launch_bounds__(256) void eig_vtu(int64_t n, int p, int tr, int64_t rw, int nblk, int with_w,
+                                               const double* __restrict__ V, const double* __restrict__ W,
+                                               const double* __restrict__ U, double* __restrict__ part) {
+    __shared__ double At[EIG_TILE], Bt[EIG_TILE], red[256];
+    const int E = p * p, nall = nblk + with_w;
+    const int64_t lo = (int64_t)blockIdx.x * rw, hi = min(n, lo + rw);
+    for (int b = 0; b < nall; ++b) {
+        const double* src = b < nblk ? V + (int64_t)b * n * p : W;
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t t0 = lo; t0 < hi; t0 += tr) {
+            const int have = (int)min((int64_t)tr, hi - t0) * p;
+            load_tile(At, src + t0 * p, have, tr * p);
+            load_tile(Bt, U + t0 * p, have, tr * p);
+            __syncthreads();
+            tile_products(p, tr, At, Bt, red, acc);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = threadIdx.x + 256 * i;
+            if (e < E) part[((int64_t)blockIdx.x * nall + b) * E + e] = acc[i];
+        }
+    }
+}
+
+// eig_combine<MUL> on W and Q = S_M W in one pass over the rows: outW = W M,
+// outQ = Q M (M = R^-1, p x p; S_M (W M) = (S_M W) M needs no product), and
+// gpart[block][c][d], the workgroup's share of outW^T outQ. The outputs may be
+// the inputs.
+__global__ __launch_bounds__(256) void eig_mul2(int64_t n, int p, int tr, int64_t rw, const double* W, const double* Q,
+                                                const double* __restrict__ M, double* outW, double* outQ,
+                                                double* __restrict__ gpart) {
+    __shared__ double At[EIG_TILE], Bt[EIG_TILE], red[256];
+    const int E = p * p;
+    const int64_t lo = (int64_t)blockIdx.x * rw, hi = min(n, lo + rw);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t t0 = lo; t0 < hi; t0 += tr) {
+        const int have = (int)min((int64_t)tr, hi - t0) * p;
+        load_tile(At, W + t0 * p, have, tr * p);
+        load_tile(Bt, Q + t0 * p, have, tr * p);
+        __syncthreads();
+        double w[8], q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = threadIdx.x + 256 * u;
+            w[u] = q[u] = 0.0;
+            if (i < have) {
+                const int r = i / p, d = i % p;
+                for (int c = 0; c < p; ++c) {
+                    const double m = M[c * p + d];
+                    w[u] = fma(At[r * p + c], m, w[u]);
+                    q[u] = fma(Bt[r * p + c], m, q[u]);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = threadIdx.x + 256 * u;
+            if (i < have) {
+                outW[t0 * p + i] = w[u];
+                outQ[t0 * p + i] = q[u];
+            }
+            if (i < tr * p) {
+                At[i] = i < have ? w[u] : 0.0;
+                Bt[i] = i < have ? q[u] : 0.0;
+            }
+        }
+        __syncthreads();
+        tile_products(p, tr, At, Bt, red, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = threadIdx.x + 256 * i;
+        if (e < E) gpart[(int64_t)blockIdx.x * E + e] = acc[i];
+    }
+}
+
+// eig_resid for r = S y - lambda S_M y: a group takes the row of S, then the
+// row of S_M, each in stored order; the partials as eig_resid's
+template <typename TA, int G, int KC>
+__global__ __launch_bounds__(256) void eig_resid_gen(int64_t n, int64_t k, const int64_t* __restrict__ rp,
+                                                     const int32_t* __restrict__ col, const TA* __restrict__ val,
+                                                     const int64_t* __restrict__ mrp, const int32_t* __restrict__ mcol,
+                                                     const TA* __restrict__ mval, const double* __restrict__ Y,
+                                                     const double* __restrict__ lam, double* __restrict__ part) {
+    constexpr int GROUPS = 256 / G;
+    __shared__ double sh[GROUPS][2 * KC];
+    const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+    for (int64_t j0 = 0; j0 < k; j0 += KC) {
+        double rr[KC], yy[KC];
+#pragma unroll
+        for (int c = 0; c < KC; ++c) rr[c] = yy[c] = 0.0;
+        for (int64_t row0 = (int64_t)blockIdx.x * GROUPS; row0 < n; row0 += (int64_t)gridDim.x * GROUPS) {
+            const int64_t row = row0 + grp;
+            double acc[KC], accm[KC];
+#pragma unroll
+            for (int c = 0; c < KC; ++c) acc[c] = accm[c] = 0.0;
+            if (row < n) {
+                const int64_t e1 = rp[row + 1];
+                for (int64_t e = rp[row] + lane; e < e1; e += G) {
+                    const double v = (double)val[e];
+                    const double* yp = Y + (int64_t)col[e] * k + j0;
+#pragma unroll
+                    for (int c = 0; c < KC; ++c) acc[c] = fma(v, yp[c], acc[c]);
+                }
+                const int64_t m1 = mrp[row + 1];
+                for (int64_t e = mrp[row] + lane; e < m1; e += G) {
+                    const double v = (double)mval[e];
+                    const double* yp = Y + (int64_t)mcol[e] * k + j0;
+#pragma unroll
+                    for (int c = 0; c < KC; ++c) accm[c] = fma(v, yp[c], accm[c]);
+                }
+            }
+#pragma unroll
+            for (int o = G / 2; o > 0; o >>= 1) {
+#pragma unroll
+                for (int c = 0; c < KC; ++c) {
+                    acc[c] += __shfl_xor(acc[c], o);
+                    accm[c] += __shfl_xor(accm[c], o);
+                }
+            }
+            if (lane == 0 && row < n) {
+#pragma unroll
+                for (int c = 0; c < KC; ++c) {
+                    const double y = Y[row * k + j0 + c];
+                    const double r = fma(-lam[j0 + c], accm[c], acc[c]);
+                    rr[c] = fma(r, r, rr[c]);
+                    yy[c] = fma(y, y, yy[c]);
+                }
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < KC; ++c) {
+                sh[grp][c] = rr[c];
+                sh[grp][KC + c] = yy[c];
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 2 * KC) {
+            double sum = 0.0;
+            for (int g = 0; g < GROUPS; ++g) sum += sh[g][threadIdx.x];
+            const int which = threadIdx.x / KC, c = threadIdx.x % KC;
+            part[((int64_t)blockIdx.x * 2 + which) * k + j0 + c] = sum;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename TA, int G>
+int eig_resid_gen_g(unsigned nb, int64_t n, int64_t k, const bsm_sym* S, const bsm_sym* SM, const double* Y,
+                    const double* lam, double* part, hipStream_t s) {
+    const TA *v = static_cast<const TA*>(S->vals), *mv = static_cast<const TA*>(SM->vals);
+    if (k % 4 == 0)
+        eig_resid_gen<TA, G, 4><<<nb, 256, 0, s>>>(n, k, S->rp, S->col, v, SM->rp, SM->col, mv, Y, lam, part);
+    else if (k % 2 == 0)
+        eig_resid_gen<TA, G, 2><<<nb, 256, 0, s>>>(n, k, S->rp, S->col, v, SM->rp, SM->col, mv, Y, lam, part);
+    else eig_resid_gen<TA, G, 1><<<nb, 256, 0, s>>>(n, k, S->rp, S->col, v, SM->rp, SM->col, mv, Y, lam, part);
+    BSM_HIP_TRY(hipGetLastError());
+    return BSM_OK;
+}
+
+// G from the longer of the two mean row lengths, the workgroups from n
+template <typename TA>
+int eig_resid_gen_launch(int64_t n, int64_t k, const bsm_sym* S, const bsm_sym* SM, const double* Y, const double* lam,
+                         double* part, unsigned* nb_out, hipStream_t s) {
+    const int g = std::max(resid_group(S, n), resid_group(SM, n));
+    const unsigned nb = resid_blocks(g, n);
+    *nb_out = nb;
+    switch (g) {
+        case 4: return eig_resid_gen_g<TA, 4>(nb, n, k, S, SM, Y, lam, part, s);
+        case 8: return eig_resid_gen_g<TA, 8>(nb, n, k, S, SM, Y, lam, part, s);
+        case 16: return eig_resid_gen_g<TA, 16>(nb, n, k, S, SM, Y, lam, part, s);
+        default: return eig_resid_gen_g<TA, 64>(nb, n, k, S, SM, Y, lam, part, s);
+    }
+}
+
+template <typename TA>
+int eigsh_gen_t(const bsm_nd_factor* f, const bsm_csr* a, const bsm_sym* S, const bsm_sym* SM, int64_t n, int nev,
+                int p, int ncv, double tol, uint64_t seed, const void* v0_dev, void* vec_dev, EigOut& res,
+                hipStream_t s) {
+    const int E = p * p;
+    const size_t np = (size_t)n * (size_t)p;
+    const unsigned eb = (unsigned)((np + 255) / 256);
+    const EigGeom g = eig_geom(n, p);
+    const int maxblk = ncv / p;
+    DBuf Vb, Wb, Qb, Tb, Yb, partb, gpartb, Cb, recb, Ub, lamb, sumb;
+    DrainOnError drain{s};
+    BSM_TRY(Vb.alloc((size_t)ncv * (size_t)n * sizeof(double), s));
+    BSM_TRY(Wb.alloc(np * sizeof(double), s));
+    BSM_TRY(Qb.alloc(np * sizeof(double), s));  // S_M V_j between the steps, S_M W inside one
+    BSM_TRY(Tb.alloc(np * sizeof(double), s));
+    BSM_TRY(Yb.alloc(np * sizeof(double), s));
+    BSM_TRY(partb.alloc(std::max((size_t)g.nb * (size_t)(maxblk + 1) * E, (size_t)REFINE_MAX_BLOCKS * 2 * p) *
+                            sizeof(double), s));
+    BSM_TRY(gpartb.alloc((size_t)g.nb * E * sizeof(double), s));
+    BSM_TRY(Cb.alloc((size_t)(maxblk + 1) * E * sizeof(double), s));
+    BSM_TRY(recb.alloc((size_t)(4 * E + 1 + p) * sizeof(double), s));  // the record, then norm2: one read
+    BSM_TRY(Ub.alloc((size_t)E * sizeof(double), s));
+    BSM_TRY(lamb.alloc((size_t)p * sizeof(double), s));
+    BSM_TRY(sumb.alloc((size_t)2 * p * sizeof(double), s));
+    double *V = Vb.as<double>(), *W = Wb.as<double>(), *Q = Qb.as<double>(), *Y = Yb.as<double>();
+    double *part = partb.as<double>(), *gpart = gpartb.as<double>(), *C = Cb.as<double>(), *rec = recb.as<double>();
+    double *U = Ub.as<double>(), *norm2 = rec + 4 * E + 1, *lamd = lamb.as<double>(), *sums = sumb.as<double>();
+    TA* T = Tb.as<TA>();
+    std::vector<double> h((size_t)4 * E + 1 + p), B((size_t)E);
+    uint32_t flags = 0;
+
+    // C = [V_0 .. V_{nblk-1} (W)]^T Q into C, the record and norm2
+    auto project = [&](int nblk, int with_w, int pass) -> int {
+        const int nall = nblk + with_w;
+        eig_vtu<<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, nblk, with_w, V, W, Q, part);
+        BSM_HIP_TRY(hipGetLastError());
+        eig_sum<<<1, 256, 0, s>>>((int)g.nb, nall * E, part, C, p, nblk - 1, with_w ? nblk : -1, pass, rec, norm2);
+        BSM_HIP_TRY(hipGetLastError());
+        return BSM_OK;
+    };
+    // Cholesky-QR twice on W in the S_M inner product, from the partials of
+    // W^T Q in gp; W and Q go through both passes together, into toW and toQ
+    auto orthonormalise = [&](const double* gp, double* toW, double* toQ) -> int {
+        eig_judge<<<1, 256, 0, s>>>((int)g.nb, p, gp, norm2, 1, rec, U);
+        BSM_HIP_TRY(hipGetLastError());
+        eig_mul2<<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, W, Q, U, W, Q, gpart);
+        BSM_HIP_TRY(hipGetLastError());
+        eig_judge<<<1, 256, 0, s>>>((int)g.nb, p, gpart, nullptr, 2, rec, U);
+        BSM_HIP_TRY(hipGetLastError());
+        eig_mul2<<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, W, Q, U, toW, toQ, gpart);
+        BSM_HIP_TRY(hipGetLastError());
+        if (read_dev(h.data(), rec, h.size() * sizeof(double), s) != hipSuccess) {
+            set_error("eigsh: reading the step's record failed");
+            return BSM_ERR_HIP;
+        }
+        BSM_REQUIRE(eig_mass_pd(p, &h[(size_t)4 * E + 1]), BSM_ERR_UNSUPPORTED,
+                    "eigsh: m is not positive definite (w^T S_M w is <= 0 or not finite)");
+        return BSM_OK;
+    };
+
+    EigLoop loop;
+    loop.init(p, nev, ncv, tol);
+    if (v0_dev) eig_cast<double, TA><<<eb, 256, 0, s>>>((int64_t)np, static_cast<const TA*>(v0_dev), W);
+    else eig_fill<TA><<<eb, 256, 0, s>>>(n, p, seed, W);
+    BSM_HIP_TRY(hipGetLastError());
+    BSM_TRY(eig_mass_launch<TA>(n, p, SM, W, Q, s));
+    stage_mark("eig_mass", s);
+    BSM_TRY(project(0, 1, 1));  // W^T Q: the Gram partials, and norm2
+    BSM_TRY(orthonormalise(part, V, Q));
+    bool have_basis = h[(size_t)4 * E] != 0.0;
+    if (!have_basis) flags |= EIG_EXHAUSTED;  // a start block without full rank spans nothing to iterate on
+    stage_mark("eig_qr", s);
+
+    const double rtol = refine_default_tol(S->max_len);
+    std::vector<uint32_t> it((size_t)p);
+    std::vector<double> be((size_t)p);
+    while (have_basis) {
+        const int j = loop.steps, nblk = j + 1;
+        eig_cast<TA, double><<<eb, 256, 0, s>>>((int64_t)np, Q, T);  // Q = S_M V_j
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_TRY(nd_refine_solve(f, a, (uint64_t)p, T, T, 5, 0.0, it.data(), be.data(), s));
+        eig_cast<double, TA><<<eb, 256, 0, s>>>((int64_t)np, T, W);
+        BSM_HIP_TRY(hipGetLastError());
+        stage_mark("eig_solve", s);  // the stage list is the last solve's, then these (bsm_stage_times)
+        for (double e : be)
+            if (!(e <= rtol)) flags |= EIG_INEXACT;
+        for (int pass = 1; pass <= 2; ++pass) {
+            BSM_TRY(eig_mass_launch<TA>(n, p, SM, W, Q, s));
+            stage_mark("eig_mass", s);
+            BSM_TRY(project(nblk, pass == 1, pass));
+            eig_combine<EIG_SUBP><<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, nblk, V, W, C, W, nullptr);
+            BSM_HIP_TRY(hipGetLastError());
+            stage_mark("eig_reorth", s);
+        }
+        BSM_TRY(eig_mass_launch<TA>(n, p, SM, W, Q, s));
+        stage_mark("eig_mass", s);
+        eig_vtu<<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, 0, 1, V, W, Q, part);  // W^T Q after the projections
+        BSM_HIP_TRY(hipGetLastError());
+        const bool room = (nblk + 1) * p <= ncv;
+        BSM_TRY(orthonormalise(part, room ? V + (size_t)nblk * np : W, Q));
+        stage_mark("eig_qr", s);
+        const bool full = h[(size_t)4 * E] != 0.0;
+        if (full) eig_mul_upper(p, &h[(size_t)2 * E], &h[(size_t)E], B.data());
+        loop.push(h.data(), full ? B.data() : nullptr);
+        if (!full) {
+            flags |= EIG_EXHAUSTED;
+            loop.ritz(&h[(size_t)3 * E]);
+            stage_mark("eig_ritz", s);
+            break;
+        }
+        if (loop.check_due(loop.steps)) {
+            loop.ritz();
+            stage_mark("eig_ritz", s);  // the stream is idle meanwhile: the host's time
+            if (loop.done()) break;
+        }
+        if (!room) break;
+    }
+    if (have_basis && loop.m_ritz != loop.m()) loop.ritz();
+
+    // the wanted pairs, lambda ascending
+    const int m = loop.m(), got = std::min(nev, m);
+    std::vector<int> order((size_t)got);
+    std::iota(order.begin(), order.end(), 0);
+    std::vector<double> lam_all((size_t)got);
+    for (int i = 0; i < got; ++i) lam_all[(size_t)i] = 1.0 / loop.theta_of(i);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lam_all[(size_t)x] < lam_all[(size_t)y]; });
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    res.lam.assign((size_t)nev, nan);
+    res.resid.assign((size_t)nev, nan);
+    if (vec_dev && got < nev) BSM_HIP_TRY(hipMemsetAsync(vec_dev, 0, (size_t)n * (size_t)nev * sizeof(TA), s));
+    std::vector<double> Z((size_t)m * p), lamc((size_t)p), sum_h((size_t)2 * p);
+    for (int c0 = 0; c0 < got; c0 += p) {
+        const int cols = std::min(p, got - c0);
+        std::fill(Z.begin(), Z.end(), 0.0);
+        std::fill(lamc.begin(), lamc.end(), 0.0);
+        for (int c = 0; c < cols; ++c) {
+            const int i = order[(size_t)(c0 + c)];
+            lamc[(size_t)c] = lam_all[(size_t)i];
+            for (int r = 0; r < m; ++r) Z[(size_t)r * p + c] = loop.s_of(i, r);
+        }
+        BSM_TRY(upload(C, Z.data(), Z.size() * sizeof(double), s));  // C holds (ncv + p) p values
+        BSM_TRY(upload(lamd, lamc.data(), lamc.size() * sizeof(double), s));
+        eig_combine<EIG_YVZ><<<g.nb, 256, 0, s>>>(n, p, g.tr, g.rw, m / p, V, nullptr, C, Y, nullptr);
+        BSM_HIP_TRY(hipGetLastError());
+        if constexpr (sizeof(TA) < sizeof(double)) {  // the residual is that of the vectors as they are returned
+            eig_cast<TA, double><<<eb, 256, 0, s>>>((int64_t)np, Y, T);
+            BSM_HIP_TRY(hipGetLastError());
+            eig_cast<double, TA><<<eb, 256, 0, s>>>((int64_t)np, T, Y);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        unsigned nb = 0;
+        BSM_TRY(eig_resid_gen_launch<TA>(n, p, S, SM, Y, lamd, part, &nb, s));
+        eig_sum<<<1, 256, 0, s>>>((int)nb, 2 * p, part, sums, p, -1, -1, 0, nullptr, nullptr);
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_HIP_TRY(read_dev(sum_h.data(), sums, sum_h.size() * sizeof(double), s));
+        for (int c = 0; c < cols; ++c) {
+            res.lam[(size_t)(c0 + c)] = lamc[(size_t)c];
+            res.resid[(size_t)(c0 + c)] = std::sqrt(sum_h[(size_t)c]) / std::sqrt(sum_h[(size_t)(p + c)]);
+        }
+        if (vec_dev) {
+            const unsigned sb = (unsigned)(((size_t)n * cols + 255) / 256);
+            eig_store_cols<TA><<<sb, 256, 0, s>>>(n, p, nev, c0, cols, Y, static_cast<TA*>(vec_dev));
+            BSM_HIP_TRY(hipGetLastError());
+        }
+    }
+    stage_mark("eig_resid", s);
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    res.info[0] = (uint32_t)loop.steps;
+    res.info[1] = (uint32_t)m;
+    res.info[2] = have_basis ? (uint32_t)loop.converged() : 0u;
+    res.info[3] = flags;
+    return BSM_OK;
+}
+
 }  // namespace
 
 int nd_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv, double tol,
@@ -550,6 +980,38 @@ int nd_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t bl
                                                              v0_dev, vec_dev, res, s)
                                            : eigsh_t<float>(f, a, S, n, (int)nev, (int)block, (int)ncv, tol, seed,
                                                             v0_dev, vec_dev, res, s);
+        BSM_TRY(rc);
+        for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
+            lam[i] = res.lam[i];
+            resid[i] = res.resid[i];
+        }
+    }
+    if (info)
+        for (int i = 0; i < 4; ++i) info[i] = res.info[i];
+    return BSM_OK;
+}
+
+int nd_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block, uint64_t ncv,
+                 double tol, uint64_t seed, const void* v0_dev, double* lam, void* vec_dev, double* resid,
+                 uint32_t* info, hipStream_t s) {
+    {
+        std::lock_guard<std::mutex> lk(f->mu);
+        BSM_REQUIRE(f->valid, BSM_ERR_INVALID, "nd factor: factor holds no values; refactor first");
+    }
+    const int64_t n = (int64_t)f->n;
+    EigOut res;
+    if (n > 0) {
+        BSM_REQUIRE(ncv <= EIG_MAX_NCV, BSM_ERR_UNSUPPORTED, "eigsh: ncv %llu is above %llu",
+                    (unsigned long long)ncv, (unsigned long long)EIG_MAX_NCV);
+        BSM_REQUIRE(m->nnz > 0, BSM_ERR_UNSUPPORTED, "eigsh: m is not positive definite (it has no stored entries)");
+        const bsm_sym *S = nullptr, *SM = nullptr;
+        BSM_TRY(sym_obtain(a, s, &S));
+        BSM_TRY(sym_obtain(m, s, &SM));
+        if (tol == 0.0) tol = eig_default_tol(a->dtype == BSM_F64);
+        const int rc = a->dtype == BSM_F64 ? eigsh_gen_t<double>(f, a, S, SM, n, (int)nev, (int)block, (int)ncv, tol,
+                                                                 seed, v0_dev, vec_dev, res, s)
+                                           : eigsh_gen_t<float>(f, a, S, SM, n, (int)nev, (int)block, (int)ncv, tol,
+                                                                seed, v0_dev, vec_dev, res, s);
         BSM_TRY(rc);
         for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
             lam[i] = res.lam[i];

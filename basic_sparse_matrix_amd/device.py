@@ -284,20 +284,24 @@ def nd_factor_solve_pcg(factor, a, b: torch.Tensor, out: torch.Tensor | None = N
 
 def nd_factor_eigsh(factor, a, nev: int, block: int = 4, ncv: int | None = None, tol: float | None = None,
                     v0: torch.Tensor | None = None, seed: int = 0, out: torch.Tensor | None = None, *,
-                    vectors: bool = True, stream=None):
+                    vectors: bool = True, stream=None, m=None):
     """``NdFactor.eigsh`` with the start block and the vectors resident in
     HBM (``bsm_dev_nd_factor_eigsh``). ``v0`` is row-major ``(n, block)`` and
     ``out`` row-major ``(n, nev)``, contiguous, of ``a``'s dtype, on the
     factor's device; ``out`` defaults to a new tensor (``None`` is returned
     with ``vectors=False``). Returns ``(lam, out, EigInfo)`` with ``lam`` a
     host array. Runs on ``stream`` and is synchronous for it; the same
-    kernels and bits as the host-buffer call."""
-    from .solver import check_eig_args, eig_info
+    kernels and bits as the host-buffer call. ``m`` (keyword only) is the
+    mass matrix of the generalised problem, as ``NdFactor.eigsh``'s
+    (``bsm_dev_nd_factor_eigsh_gen``)."""
+    from .solver import check_eig_args, check_eig_mass, eig_info
     from .sparse import _raise_for
 
     h = factor._h()
     n = factor.n
-    m, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "nd_factor_eigsh")
+    ncv_use, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "nd_factor_eigsh")
+    if m is not None:
+        check_eig_mass(a, m, n, "nd_factor_eigsh")
     want = TORCH_DT[np.dtype(a.dtype)]
     if n == 0:
         nev = 0
@@ -318,11 +322,20 @@ def nd_factor_eigsh(factor, a, nev: int, block: int = 4, ncv: int | None = None,
     resid = np.zeros(nev, dtype=np.float64)
     info = np.zeros(4, dtype=np.uint32)
     dev = a._device()
+    mdev = m._device() if m is not None else None
     if n:
-        _raise_for(_lib.require_device().bsm_dev_nd_factor_eigsh(
-            h, dev.handle, nev, block, m, tol_used, seed, _p(v0) if v0 is not None else None, _lib.ptr(lam),
-            _p(out) if out is not None else None, _lib.ptr(resid), _lib.ptr(info), _stream(stream)))
-    return lam, out, eig_info(a, dev, lam, resid, info, tol_used)
+        lib = _lib.require_device()
+        v0_p = _p(v0) if v0 is not None else None
+        out_p = _p(out) if out is not None else None
+        if m is None:
+            _raise_for(lib.bsm_dev_nd_factor_eigsh(h, dev.handle, nev, block, ncv_use, tol_used, seed, v0_p,
+                                                   _lib.ptr(lam), out_p, _lib.ptr(resid), _lib.ptr(info),
+                                                   _stream(stream)))
+        else:
+            _raise_for(lib.bsm_dev_nd_factor_eigsh_gen(h, dev.handle, mdev.handle, nev, block, ncv_use, tol_used,
+                                                       seed, v0_p, _lib.ptr(lam), out_p, _lib.ptr(resid),
+                                                       _lib.ptr(info), _stream(stream)))
+    return lam, out, eig_info(a, dev, lam, resid, info, tol_used, m, mdev)
 
 
 def nd_factor_inv_diag(factor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:

@@ -211,8 +211,25 @@ def check_eig_args(a: Csr, n: int, nev, block, ncv, tol, seed, what: str) -> tup
     return m, float(tol) if tol is not None else (2.0 ** -26 if a.dtype == np.float64 else 2.0 ** -12)
 
 
-def eig_info(a: Csr, dev, lam, resid, info, tol_used) -> EigInfo:
+def check_eig_mass(a: Csr, m: Csr, n: int, what: str) -> None:
+    """The host-side checks of ``eigsh``'s mass matrix ``m`` against ``a``."""
+    if not isinstance(m, Csr):
+        raise TypeError(f"{what}: m must be a Csr, got {type(m).__name__}")
+    if m.dtype != a.dtype:
+        raise TypeError(f"{what}: m must have a's dtype {a.dtype}, got {m.dtype}")
+    if m.dims.rows != n or m.dims.cols != n:
+        raise MatErr(MatErrKind.IncorrectDimensions)
+
+
+def eig_info(a: Csr, dev, lam, resid, info, tol_used, m: Csr | None = None, mdev=None) -> EigInfo:
+    """``EigInfo`` of a call's results. ``converged`` is ``resid <= 2 tol
+    ||S||inf`` on a finite ``lam``; with a mass matrix ``m`` it is the
+    normwise backward error test ``resid <= 2 tol (||S||inf + |lam|
+    ||S_M||inf)``."""
     bound = 2.0 * tol_used * sym_norm_inf(a, dev)
+    if m is not None:
+        with np.errstate(invalid="ignore"):
+            bound = 2.0 * tol_used * (sym_norm_inf(a, dev) + np.abs(lam) * sym_norm_inf(m, mdev))
     with np.errstate(invalid="ignore"):
         conv = np.isfinite(lam) & (resid <= bound)
     return EigInfo(int(info[0]), int(info[1]), resid, conv, bool(info[3] & 1), bool(info[3] & 2), tol_used)
@@ -356,7 +373,7 @@ class NdFactor:
         return out, PcgInfo(iters, berr, berr <= tol_used, (flags & 1) != 0, tol_used)
 
     def eigsh(self, a: Csr, nev: int, block: int = 4, ncv: int | None = None, tol: float | None = None,
-              v0: Dense | None = None, seed: int = 0, *, vectors: bool = True):
+              v0: Dense | None = None, seed: int = 0, *, vectors: bool = True, m: Csr | None = None):
         """The ``nev`` smallest eigenvalues of ``S`` (``a``'s lower triangle
         mirrored, as ``solve_refined`` defines it) and their eigenvectors, by
         block shift-invert Lanczos on this factor (``bsm_nd_factor_eigsh``):
@@ -373,10 +390,27 @@ class NdFactor:
         There is no restart: call again with ``v0`` made of the first
         ``block`` vectors and a larger ``ncv``. An eigenvalue of multiplicity
         above ``block`` is found ``block`` times at most (a long run may pick
-        up a further copy from rounding; do not count on it)."""
+        up a further copy from rounding; do not count on it).
+
+        ``m`` (keyword only): a mass matrix, for the generalised problem ``S y
+        = lam S_M y`` of finite elements and volumes (``bsm_nd_factor_eigsh_gen``;
+        SciPy's ``eigsh(A, k, M=m, sigma=0)``). ``m`` is an ``n x n`` ``Csr`` of
+        ``a``'s dtype with any pattern; ``S_M`` is its lower triangle mirrored
+        and must be positive definite (else the call raises, "m is not
+        positive definite"). The loop is the same in the ``S_M`` inner
+        product; the vectors are normalised to ``y^T S_M y = 1`` and
+        ``EigInfo.resid`` is ``||S y - lam S_M y||2 / ||y||2``. The loop stops
+        on the estimates ``est <= tol``, which bound ``resid`` by ``tol
+        ||S||inf sqrt(mu_max / mu_min)`` (``mu``: the extreme eigenvalues of
+        ``S_M``), while ``EigInfo.converged`` is the normwise backward error
+        test ``resid <= 2 tol (||S||inf + |lam| ||S_M||inf)``: for an
+        ill-conditioned ``m`` a smaller ``tol`` may be needed for
+        ``converged``. Without ``m`` the call is unchanged."""
         h = self._h()
         n = self.n
-        m, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "NdFactor.eigsh")
+        ncv_use, tol_used = check_eig_args(a, n, nev, block, ncv, tol, seed, "NdFactor.eigsh")
+        if m is not None:
+            check_eig_mass(a, m, n, "NdFactor.eigsh")
         v0_cols = None
         if v0 is not None:
             dims = v0.get_dims()
@@ -397,13 +431,19 @@ class NdFactor:
         info = np.zeros(4, dtype=np.uint32)
         out = Dense.new_default_with_dims(nev, n, dtype=a.dtype) if vectors else None
         dev = a._device()
+        mdev = m._device() if m is not None else None
         if n:
             lib = _lib.require_device()
-            _raise_for(lib.bsm_nd_factor_eigsh(h, dev.handle, nev, block, m, tol_used, seed,
-                                               _lib.ptr_array(v0_cols) if v0_cols is not None else None,
-                                               _lib.ptr(lam), _lib.ptr_array(out.data) if vectors else None,
-                                               _lib.ptr(resid), _lib.ptr(info)))
-        return lam, out, eig_info(a, dev, lam, resid, info, tol_used)
+            v0_p = _lib.ptr_array(v0_cols) if v0_cols is not None else None
+            out_p = _lib.ptr_array(out.data) if vectors else None
+            if m is None:
+                _raise_for(lib.bsm_nd_factor_eigsh(h, dev.handle, nev, block, ncv_use, tol_used, seed, v0_p,
+                                                   _lib.ptr(lam), out_p, _lib.ptr(resid), _lib.ptr(info)))
+            else:
+                _raise_for(lib.bsm_nd_factor_eigsh_gen(h, dev.handle, mdev.handle, nev, block, ncv_use, tol_used,
+                                                       seed, v0_p, _lib.ptr(lam), out_p, _lib.ptr(resid),
+                                                       _lib.ptr(info)))
+        return lam, out, eig_info(a, dev, lam, resid, info, tol_used, m, mdev)
 
     def refactor(self, a: Csr) -> None:
         """New values on the same pattern (``bsm_nd_factor_refactor``): the

@@ -450,6 +450,49 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    factor's device, ROW-major n x block and n x nev of a's dtype (either may
  *    be NULL), on `stream`; synchronous for that stream. The same kernels and
  *    bits as the host call.
+ *  - bsm_nd_factor_eigsh_gen: the generalised problem S y = lambda S_M y with
+ *    a mass matrix m (finite elements and volumes: K x = lambda M x): the nev
+ *    smallest lambda, ascending. S_M is m's lower triangle mirrored, exactly as
+ *    S is a's (entries above the diagonal are ignored; the copy is kept on m's
+ *    handle); m is an n x n bsm_csr of a's dtype on the factor's device with
+ *    any pattern. m == NULL calls bsm_nd_factor_eigsh: the same bits. S_M must
+ *    be positive definite; a singular mass matrix (constraints, massless
+ *    degrees of freedom), a shift sigma != 0 and restarts are out of scope.
+ *    The loop is bsm_nd_factor_eigsh's in the S_M inner product, in which the
+ *    operator A^-1 S_M is self-adjoint: every block is made S_M-orthonormal;
+ *    a step is W = A^-1 (S_M V_j) by the same refined solve; norm2_c = w_c^T
+ *    S_M w_c; classical Gram-Schmidt twice with C = V^T (S_M W), W -= V C;
+ *    Cholesky-QR twice on G = W^T S_M W with the same rank rule; B_{j+1} = R2
+ *    R1. Since S_M (W R^-1) = (S_M W) R^-1, W and S_M W go through the two
+ *    W R^-1 passes together and the step ends with S_M V_{j+1} for the next
+ *    one: three products with S_M per step (after the solve and after each
+ *    projection pass) and one for the start block; S_M V is not kept for the
+ *    basis. T, the Ritz solve, est, the stop rule, lambda = 1 / theta, info and
+ *    the flags are bsm_nd_factor_eigsh's. The vectors are normalised to y^T
+ *    S_M y = 1, without a sign convention, and rounded to f32 for an f32 a.
+ *    resid[i] = ||S y_i - lam_i S_M y_i||2 / ||y_i||2, formed anew in f64 from
+ *    the vectors as they are returned (with S_M = I: bsm_nd_factor_eigsh's).
+ *    With e = A^-1 S_M y - theta y, S y - lam S_M y = -lam S e and ||e||_M =
+ *    est theta ||y||_M, so a pair with est <= tol has resid <= tol ||S||inf
+ *    sqrt(mu_max / mu_min) up to rounding, mu the extreme eigenvalues of S_M:
+ *    the loop stops on est, and an ill-conditioned m may need a smaller tol
+ *    for a wanted residual. Errors, all before any device work and with every
+ *    output untouched: bsm_nd_factor_eigsh's; m not f32/f64 -> BSM_ERR_INVALID;
+ *    m's dtype not a's -> BSM_ERR_INVALID; m on another device ->
+ *    BSM_ERR_INVALID; m not n x n -> BSM_ERR_DIMENSIONS. A norm2_c that is <=
+ *    0 or not finite (of the start block or of a step; a zero column of v0
+ *    reads the same), or an m without stored entries, means that S_M is not
+ *    positive definite: BSM_ERR_UNSUPPORTED ("m is not positive definite"),
+ *    as bsm_nd_factor_create reports it for a, every output untouched; an
+ *    indefinite S_M that no block exposes ends as "exhausted". Temporaries:
+ *    bsm_nd_factor_eigsh's plus one n x block f64 array, (ncv + 4 block) n f64
+ *    in all (S_M V_j between the steps and S_M W inside one share it), the
+ *    partials and the refined solve's. The same call gives the same bits (the
+ *    products with S_M take a row's entries in stored order by a fixed number
+ *    of lanes and a fixed xor tree; the partials as above; no floating-point
+ *    atomics).
+ *  - bsm_dev_nd_factor_eigsh_gen: the same with v0 and the vectors in HBM, as
+ *    bsm_dev_nd_factor_eigsh; m == NULL calls that function.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -488,6 +531,12 @@ int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, 
 int bsm_dev_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
                             double tol, uint64_t seed, const void* v0, double* lam, void* vecs, double* resid,
                             uint32_t* info, void* stream);
+int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
+                            uint64_t ncv, double tol, uint64_t seed, const void* const* v0_cols, double* lam,
+                            void* const* vec_cols, double* resid, uint32_t* info);
+int bsm_dev_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev,
+                                uint64_t block, uint64_t ncv, double tol, uint64_t seed, const void* v0, double* lam,
+                                void* vecs, double* resid, uint32_t* info, void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

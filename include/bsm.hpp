@@ -993,6 +993,43 @@ public:
         return out;
     }
 
+    /// eigsh for the generalised problem S y = lam S_M y (bsm_nd_factor_eigsh_gen):
+    /// m is the mass matrix, n x n of a's type with any pattern, S_M its lower
+    /// triangle mirrored, which must be positive definite (else the call throws
+    /// "m is not positive definite"). The same loop in the S_M inner product:
+    /// the vectors have y^T S_M y = 1 and resid is ||S y - lam S_M y||2 / ||y||2.
+    /// The other arguments and the result are eigsh's.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    Eig<U> eigsh_gen(const Csr<U>& a, const Csr<U>& m, size_t nev, size_t block = 4, size_t ncv = 0, double tol = 0,
+                     uint64_t seed = 0, const Dense<U>* v0 = nullptr) const {
+        if (!(tol >= 0)) throw std::invalid_argument("NdFactor::eigsh_gen: tol must be >= 0 (0 = the default)");
+        if (a.get_dims().rows != n_ || a.get_dims().cols != n_ || m.get_dims().rows != n_ ||
+            m.get_dims().cols != n_ || (v0 && (v0->get_dims().rows != n_ || v0->get_dims().cols != block)))
+            throw Panic("NdFactor::eigsh_gen: IncorrectDimensions");
+        if (n_ == 0) nev = 0;
+        Eig<U> out{std::vector<double>(nev), Dense<U>::new_default_with_dims(nev, n_), std::vector<double>(nev)};
+        out.tol = tol > 0 ? tol : (sizeof(U) == 8 ? 0x1p-26 : 0x1p-12);
+        if (n_ == 0) return out;
+        std::vector<const void*> in_cols(v0 ? block : 0);
+        for (size_t j = 0; j < in_cols.size(); ++j) in_cols[j] = v0->get_col(j).data();
+        std::vector<void*> out_cols(nev);
+        for (size_t j = 0; j < nev; ++j) out_cols[j] = out.vectors.get_col_mut(j).data();
+        uint32_t info[4] = {0, 0, 0, 0};
+        double none = 0.0;  // nev == 0 is refused by the library, not by a null pointer here
+        auto h = a.device();
+        auto hm = m.device();
+        detail::check(bsm_nd_factor_eigsh_gen(f_.get(), h.get(), hm.get(), nev, block, ncv, out.tol, seed,
+                                              v0 ? in_cols.data() : nullptr, nev ? out.lam.data() : &none,
+                                              out_cols.data(), nev ? out.resid.data() : &none, info));
+        out.steps = info[0];
+        out.ncv_used = info[1];
+        out.converged = info[2];
+        out.exhausted = (info[3] & 1u) != 0;
+        out.inexact = (info[3] & 2u) != 0;
+        return out;
+    }
+
     /// diag(A^-1) in A's order (bsm_nd_factor_selinv): the selected inverse by
     /// the Takahashi recursion over the fronts; the same bits on every call.
     std::vector<T> inv_diag() const {

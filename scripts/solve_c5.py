@@ -169,6 +169,10 @@ def main():
     ap.add_argument("--eig", type=int, default=0, metavar="NEV",
                     help="only the eigsh record: the NEV smallest eigenpairs on the kept factor, f64 and f32 factor, "
                          "block 4 and 8 (profiles/nd_eig_c5.jsonl)")
+    ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
+                    help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
+                         "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
+                         "tridiag(1/6, 4/6, 1/6); none: the same record without m, the yardstick of the other two")
     args = ap.parse_args()
     dt = np.float64 if args.dtype == "f64" else np.float32
     g = args.g
@@ -178,7 +182,7 @@ def main():
     B = Dense.from_columns([b])
     if args.eig:
         _lib.stage_timing(True)
-        print(json.dumps(nd_eig_ops(A, B, args.eig, max(args.reps, 1), g)), flush=True)
+        print(json.dumps(nd_eig_ops(A, B, args.eig, max(args.reps, 1), g, args.mass)), flush=True)
         return
     fixture = None
     fx_path = os.path.join(ROOT, "tests", "golden", f"c5_poisson_{g}.json")
@@ -533,7 +537,33 @@ def nd_pcg_ops(A, B, reps, pattern):
     return out
 
 
-def nd_eig_ops(A, B, nev, reps, g):
+def mass_matrix(g, kind):
+    """The mass matrix of --mass on the g x g grid, built on the host: (Csr, the entries of S_M; both are
+    stored whole, so their lower triangle mirrored is themselves)."""
+    n = g * g
+    if kind == "lumped":  # splitmix64 of the row index, 53 bits into [0.5, 2)
+        z = np.arange(n, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+        d = 0.5 + 1.5 * ((z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53)
+        idx = np.arange(n, dtype=np.uint64)
+        return Csr.from_csr_arrays((n, n), np.arange(n + 1, dtype=np.uint64), idx, d), n
+    i, j = np.divmod(np.arange(n, dtype=np.int64), g)
+    rows, cols, vals = [], [], []
+    for di in (-1, 0, 1):  # ascending columns inside a row
+        for dj in (-1, 0, 1):
+            ok = (i + di >= 0) & (i + di < g) & (j + dj >= 0) & (j + dj < g)
+            rows.append(np.nonzero(ok)[0])
+            cols.append(((i + di) * g + j + dj)[ok])
+            vals.append(np.full(int(ok.sum()), (4.0 if di == 0 else 1.0) / 6.0 * ((4.0 if dj == 0 else 1.0) / 6.0)))
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    order = np.lexsort((cols, rows))
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.uint64)
+    return Csr.from_csr_arrays((n, n), rp, cols[order].astype(np.uint64), vals[order]), int(rows.size)
+
+
+def nd_eig_ops(A, B, nev, reps, g, mass=None):
     """The nev smallest eigenpairs of the f64 system by NdFactor.eigsh (block
     shift-invert Lanczos), f64 and f32 factor, block 4 and 8, vectors left on
     the device; host wall ms around synchronous calls (medians of `reps`).
@@ -546,29 +576,43 @@ def nd_eig_ops(A, B, nev, reps, g):
     twice; eig_ritz: the host's Ritz check of the largest T, the stream idle
     meanwhile; eig_resid: Y = V Z and the residuals). solve_share: steps x the
     median wall ms of a `block`-column device.nd_factor_solve_refined, over
-    wall ms. reorth_GBs: 4 n ncv_used 8 bytes over the last step's eig_reorth."""
+    wall ms. reorth_GBs: 4 n ncv_used 8 bytes over the last step's eig_reorth.
+    With `mass` (--mass) the record is the generalised problem's, block 4
+    alone: eig_mass is the last step's three products with S_M, eig_qr holds
+    the Gram matrix W^T S_M W and the two passes over W and S_M W, the lam
+    errors of `consistent` are against (k_p + k_q) / (m_p m_q), k_p = 2 - 2
+    cos(p pi / (g + 1)), m_p = (4 + 2 cos(p pi / (g + 1))) / 6 (none for
+    `lumped`), and mass_GBs is the byte model of a product (the entries of S_M,
+    12 bytes each for f64, its row pointers, and W read and S_M W written once)
+    over a third of eig_mass. `none` is the same record without m."""
     import torch
 
     from basic_sparse_matrix_amd import cholesky_nd, device
 
     n = g * g
-    exact = np.sort((4.0 - 2.0 * np.cos(np.arange(1, 40) * np.pi / (g + 1))[:, None]
-                     - 2.0 * np.cos(np.arange(1, 40) * np.pi / (g + 1))[None, :]).ravel())[:nev]
+    cs = np.cos(np.arange(1, 40) * np.pi / (g + 1))
+    exact = np.sort((4.0 - 2.0 * cs[:, None] - 2.0 * cs[None, :]).ravel())[:nev]
+    M, m_nnz = (None, 0) if mass in (None, "none") else mass_matrix(g, mass)
+    if mass == "consistent":
+        mp = (4.0 + 2.0 * cs) / 6.0
+        exact = np.sort((((2.0 - 2.0 * cs)[:, None] + (2.0 - 2.0 * cs)[None, :]) / (mp[:, None] * mp[None, :])).ravel())[:nev]
     med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
     out = {"metric": "C5 nd factor: the smallest eigenpairs by block shift-invert Lanczos (host wall ms, medians)",
            "config": {"g": g, "nev": nev, "calls": reps, "ncv": 128}, "cases": {}}
+    if mass is not None:
+        out["config"]["mass"] = mass
     for fdt in (np.float64, np.float32):
         with cholesky_nd(A, factor_dtype=fdt) as f:
-            for block in (4, 8):
+            for block in ((4, 8) if mass is None else (4,)):
                 y = torch.empty((n, nev), dtype=torch.float64, device="cuda")
                 bd = torch.ones((n, block), dtype=torch.float64, device="cuda")
                 xd = torch.empty_like(bd)
-                device.nd_factor_eigsh(f, A, nev, block=block, out=y)  # builds S, warms the temporaries
+                device.nd_factor_eigsh(f, A, nev, block=block, out=y, m=M)  # builds S (S_M), warms the temporaries
                 device.nd_factor_solve_refined(f, A, bd, out=xd)
                 t_eig, t_ref, st = [], [], []
                 for _ in range(reps):
                     t0 = time.perf_counter()
-                    lam, _, info = device.nd_factor_eigsh(f, A, nev, block=block, out=y)
+                    lam, _, info = device.nd_factor_eigsh(f, A, nev, block=block, out=y, m=M)
                     t_eig.append(time.perf_counter() - t0)
                     st.append(_lib.stage_times())
                     for _ in range(3):
@@ -577,8 +621,10 @@ def nd_eig_ops(A, B, nev, reps, g):
                         t_ref.append(time.perf_counter() - t0)
                 stage = lambda k: round(float(np.median([s_.get(k, 0.0) for s_ in st])), 4)  # noqa: E731
                 stages = {k: stage(k) for k in ("eig_solve", "eig_reorth", "eig_qr", "eig_ritz", "eig_resid")}
+                if M is not None:
+                    stages["eig_mass"] = stage("eig_mass")
                 reorth_bytes = 4.0 * n * info.ncv_used * 8
-                out["cases"][f"{np.dtype(fdt).name}_factor_block{block}"] = {
+                case = out["cases"][f"{np.dtype(fdt).name}_factor_block{block}"] = {
                     "steps": info.steps, "ncv_used": info.ncv_used, "converged": int(info.converged.sum()),
                     "exhausted": info.exhausted, "inexact": info.inexact, "tol": info.tol, "eigsh_ms": med(t_eig),
                     "eigsh_ms_min_max": [round(1e3 * min(t_eig), 3), round(1e3 * max(t_eig), 3)],
@@ -588,8 +634,13 @@ def nd_eig_ops(A, B, nev, reps, g):
                     "reorth_GBs": round(reorth_bytes / (stages["eig_reorth"] * 1e-3) / 1e9, 1)
                     if stages["eig_reorth"] > 0 else None,
                     "resid": [float(r) for r in info.resid],
-                    "lam_err_vs_analytic": [float(e) for e in np.abs(lam - exact)],
+                    "lam_err_vs_analytic": [float(e) for e in np.abs(lam - exact)] if mass != "lumped" else None,
                 }
+                if M is not None:
+                    mass_bytes = 12.0 * m_nnz + 8.0 * n + 2.0 * n * block * 8
+                    case["mass_GBs"] = round(mass_bytes / (stages["eig_mass"] / 3 * 1e-3) / 1e9, 1) \
+                        if stages["eig_mass"] > 0 else None
+                    case["lam"] = [float(v) for v in lam]
     return out
 
 
