@@ -409,6 +409,14 @@ int nd_factor_export(const bsm_nd_factor* f, bsm_csr** l, bsm_csr** l_star, hipS
 // the first of them at *first_miss (their vals are 0).
 int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const uint64_t* rows_dev,
                      const uint64_t* cols_dev, void* vals_dev, uint64_t* n_miss, uint64_t* first_miss, hipStream_t s);
+// The factor of P (S + sign W W^T) P^T in place (sign = +1 / -1, 1 <= k <= 16
+// checked by the caller). W column-compressed on the device: colptr (k + 1),
+// rows (A's order, < n, nnz_w of them), vals (f's src_dtype), no stored zeros.
+// *n_miss columns lie outside the pattern, the first of them *first_miss:
+// nothing was written then. Synchronous on s.
+int nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, uint64_t nnz_w, const int64_t* colptr_dev,
+                     const uint64_t* rows_dev, const void* vals_dev, uint64_t* n_miss, uint64_t* first_miss,
+                     hipStream_t s);
 // mixed precision on a kept factor (kernels_refine.hip)
 // n float values into the other float dtype, round-to-nearest (async on s)
 int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s);

@@ -1390,6 +1390,70 @@ int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream)
     return nd_factor_selinv(f, diag, 0, nullptr, nullptr, nullptr, &n_miss, &first, static_cast<hipStream_t>(stream));
 }
 
+int bsm_nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                         const void* vals) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(k == 0 || col_ptr, BSM_ERR_INVALID, "null argument (col_ptr)");
+    BSM_REQUIRE(sign == 1 || sign == -1, BSM_ERR_INVALID, "nd factor updown: sign must be +1 or -1, got %d", sign);
+    BSM_REQUIRE(k == 0 || col_ptr[0] == 0, BSM_ERR_INVALID, "nd factor updown: col_ptr[0] must be 0, got %llu",
+                k ? (unsigned long long)col_ptr[0] : 0ull);
+    for (uint64_t c = 0; c < k; ++c) {
+        BSM_REQUIRE(col_ptr[c] <= col_ptr[c + 1], BSM_ERR_INVALID,
+                    "nd factor updown: col_ptr is not ascending at column %llu", (unsigned long long)c);
+        BSM_REQUIRE(col_ptr[c] == col_ptr[c + 1] || (rows && vals), BSM_ERR_INVALID, "null argument (rows or vals)");
+        for (uint64_t e = col_ptr[c] + 1; e < col_ptr[c + 1]; ++e)
+            BSM_REQUIRE(rows[e - 1] < rows[e], BSM_ERR_INVALID,
+                        "nd factor updown: rows must be strictly ascending within a column (column %llu, entries "
+                        "%llu and %llu are rows %llu and %llu)",
+                        (unsigned long long)c, (unsigned long long)(e - 1), (unsigned long long)e,
+                        (unsigned long long)rows[e - 1], (unsigned long long)rows[e]);
+    }
+    BSM_REQUIRE(k <= 16, BSM_ERR_UNSUPPORTED, "nd factor updown: k = %llu columns, at most 16 in one call",
+                (unsigned long long)k);
+    const uint64_t nnz = k ? col_ptr[k] : 0;
+    for (uint64_t e = 0; e < nnz; ++e)
+        BSM_REQUIRE(rows[e] < f->n, BSM_ERR_OUT_OF_BOUNDS,
+                    "nd factor updown: entry %llu is row %llu, the matrix is %llu x %llu", (unsigned long long)e,
+                    (unsigned long long)rows[e], (unsigned long long)f->n, (unsigned long long)f->n);
+    // stored zeros are no-ops: they neither start a column's path nor count for its pattern
+    const size_t es = dtype_size(f->src_dtype);
+    std::vector<int64_t> cp(k + 1, 0);
+    std::vector<uint64_t> rw;
+    std::vector<char> vl;
+    rw.reserve(nnz);
+    vl.reserve(nnz * es);
+    for (uint64_t c = 0; c < k; ++c) {
+        for (uint64_t e = col_ptr[c]; e < col_ptr[c + 1]; ++e) {
+            const char* v = static_cast<const char*>(vals) + e * es;
+            const bool zero = f->src_dtype == BSM_F64 ? *reinterpret_cast<const double*>(v) == 0.0
+                                                      : *reinterpret_cast<const float*>(v) == 0.0f;
+            if (zero) continue;
+            rw.push_back(rows[e]);
+            vl.insert(vl.end(), v, v + es);
+        }
+        cp[c + 1] = (int64_t)rw.size();
+    }
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf dp, dr, dvl;
+    if (!rw.empty()) {
+        BSM_TRY(dp.alloc((size_t)(k + 1) * 8, s));
+        BSM_TRY(dr.alloc(rw.size() * 8, s));
+        BSM_TRY(dvl.alloc(vl.size(), s));
+        BSM_TRY(h2d_staged(dp.p, cp.data(), (size_t)(k + 1) * 8, s));
+        BSM_TRY(h2d_staged(dr.p, rw.data(), rw.size() * 8, s));
+        BSM_TRY(h2d_staged(dvl.p, vl.data(), vl.size(), s));
+    }
+    uint64_t n_miss = 0, first = 0;
+    BSM_TRY(nd_factor_updown(f, sign, k, rw.size(), dp.as<int64_t>(), dr.as<uint64_t>(), dvl.p, &n_miss, &first, s));
+    BSM_REQUIRE(n_miss == 0, BSM_ERR_INVALID,
+                "nd factor updown: %llu of %llu columns lie outside the pattern (an entry is neither an own column "
+                "nor a front row of the front owning the column's first vertex in the new order); the first is "
+                "column %llu",
+                (unsigned long long)n_miss, (unsigned long long)k, (unsigned long long)first);
+    return BSM_OK;
+}
+
 int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
     std::lock_guard<std::mutex> lk(f->mu);

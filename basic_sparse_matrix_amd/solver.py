@@ -259,15 +259,17 @@ class NdFactor:
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
-    __slots__ = ("handle", "n", "dtype")
+    __slots__ = ("handle", "n", "dtype", "src_dtype")
 
-    def __init__(self, handle: int):
+    def __init__(self, handle: int, src_dtype=None):
         lib = _lib.load()
         self.handle = handle
         n, d = ctypes.c_uint64(), ctypes.c_int()
         _lib.check(lib.bsm_nd_factor_info(handle, ctypes.byref(n), ctypes.byref(d), None, None))
         self.n = n.value
         self.dtype = _lib.CODE_DTYPES[d.value]
+        # the factored matrix's dtype (update / downdate take W in it)
+        self.src_dtype = self.dtype if src_dtype is None else np.dtype(src_dtype)
 
     def _h(self) -> int:
         if not self.handle:
@@ -460,6 +462,57 @@ class NdFactor:
         dev = a._device()
         _raise_for(_lib.require_device().bsm_nd_factor_refactor(h, dev.handle))
 
+    def _updown(self, w: Csr, sign: int, what: str) -> None:
+        h = self._h()
+        if w.dims.rows != self.n:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        want = self.src_dtype
+        if w.dtype != want:
+            raise TypeError(f"NdFactor.{what}: needs Csr<{want}> (the factored matrix's dtype), got {w.dtype}")
+        k = w.dims.cols
+        rp, ci, v = w._csr_arrays()
+        rows = np.repeat(np.arange(self.n, dtype=np.uint64), np.diff(np.asarray(rp).astype(np.int64)))
+        cols = np.asarray(ci).astype(np.int64)
+        order = np.argsort(cols, kind="stable")  # column-compressed: rows stay ascending within a column
+        col_ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=k))]).astype(np.uint64)
+        r = np.ascontiguousarray(rows[order])
+        vals = np.ascontiguousarray(np.asarray(v, dtype=want)[order])
+        _raise_for(_lib.require_device().bsm_nd_factor_updown(h, sign, k, _lib.ptr(col_ptr), _lib.ptr(r),
+                                                              _lib.ptr(vals)))
+
+    def update(self, w: Csr) -> None:
+        """The factor of ``P (S + W W^T) P^T`` in place
+        (``bsm_nd_factor_updown``), ``S`` the matrix this was the factor of
+        and ``w`` a ``Csr`` of shape ``n x k``, ``1 <= k <= 16``, of the
+        FACTORED MATRIX's dtype (else ``TypeError``; another row count raises
+        ``MatErr(IncorrectDimensions)``). Only the fronts on the paths from
+        ``w``'s columns to the root of the separator tree are rewritten: a
+        few launches instead of a ``refactor``. Afterwards ``solve``,
+        ``logdet``, ``l()``, the selected inverse, ``solve_refined``,
+        ``solve_pcg`` and ``eigsh`` see the new factor, and ``nnz_l`` is 0
+        until the next ``l()``.
+
+        Which columns are inside: take a column's entry whose vertex comes
+        first in the new order (``perm``), in tree node ``N``; every other
+        entry must be one of ``N``'s own columns or front rows. Always inside:
+        a diagonal column ``alpha e_i``, and a vertex together with any of its
+        neighbours in ``S``'s graph that come LATER in the new order (an edge
+        ``sqrt(c) (e_i - e_j)`` of a stored ``(i, j)``; an element's clique
+        seen from its first vertex). A column outside raises the error for
+        ``BSM_ERR_INVALID`` naming how many columns and the first one, before
+        anything is written; a row ``>= n`` raises ``MatErr(OutOfBounds)``,
+        ``k > 16`` the error for ``BSM_ERR_UNSUPPORTED``. Stored zeros and
+        empty columns are no-ops. The same call on the same factor gives the
+        same bits."""
+        self._updown(w, 1, "update")
+
+    def downdate(self, w: Csr) -> None:
+        """The factor of ``P (S - W W^T) P^T`` in place: :meth:`update`'s
+        arguments and errors. A ``w`` that leaves the matrix not positive
+        definite raises as :func:`cholesky_nd` does, found by a dry pass that
+        writes only scratch: the factor keeps its bits and stays valid."""
+        self._updown(w, -1, "downdate")
+
     def logdet(self) -> float:
         """``log det A = 2 sum log L_ii`` (``bsm_nd_factor_logdet``), summed in
         f64 in a fixed order: the same bits on every call."""
@@ -603,7 +656,7 @@ def cholesky_nd(a: Csr, factor_dtype=None) -> NdFactor:
     else:
         _raise_for(lib.bsm_nd_factor_create_as(dev.handle, _lib.DTYPE_CODES[np.dtype(factor_dtype)],
                                                ctypes.byref(out)))
-    return NdFactor(out.value)
+    return NdFactor(out.value, a.dtype)
 
 
 def nd_analyse(n: int, row_ptr, col_idx, leaf: int = 256) -> dict:

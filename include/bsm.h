@@ -493,6 +493,39 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    atomics).
  *  - bsm_dev_nd_factor_eigsh_gen: the same with v0 and the vectors in HBM, as
  *    bsm_dev_nd_factor_eigsh; m == NULL calls that function.
+ *  - bsm_nd_factor_updown: the rank-k update (sign = +1) or downdate
+ *    (sign = -1) of the kept factor: afterwards f is the factor of
+ *    P (S + sign W W^T) P^T, S the matrix it was the factor of. Only the fronts
+ *    on the paths from W's columns to the root of the separator tree are
+ *    rewritten (14 of 15,397 at C5 for one edge), by the column-by-column method
+ *    (Gill, Golub, Murray, Saunders C1), the k columns in column order at every
+ *    pivot. W is n x k, column-compressed on the host: col_ptr has k + 1
+ *    entries, rows (A's order) is strictly ascending within a column, vals has
+ *    the FACTORED MATRIX's dtype (an f32 factor of an f64 matrix rounds them
+ *    once). 1 <= k <= 16; larger ranks call again. Which W: with a column's
+ *    entry of the smallest new index (bsm_nd_factor_perm) in tree node N,
+ *    every other entry must be an own column of N or one of N's front rows.
+ *    Always inside: a diagonal column alpha e_i, and a vertex with any of its
+ *    neighbours in S's graph that come later in the new order (an edge
+ *    sqrt(c) (e_i - e_j) of a stored (i, j); an element's clique seen from its
+ *    first vertex). Errors, in this order, all before any device write: a null
+ *    f, a null among col_ptr / rows / vals where they are read, a sign that
+ *    is neither +1 nor -1, col_ptr not ascending from 0 or rows not strictly
+ *    ascending within a column -> BSM_ERR_INVALID; k > 16 ->
+ *    BSM_ERR_UNSUPPORTED; a row >= n -> BSM_ERR_OUT_OF_BOUNDS; a handle
+ *    without values (a failed refactor) -> BSM_ERR_INVALID as for the solves;
+ *    a column outside the pattern -> BSM_ERR_INVALID naming how many columns
+ *    and the first one; a downdate that leaves the matrix not positive
+ *    definite (found by a dry pass of the same arithmetic that writes only
+ *    scratch) -> BSM_ERR_UNSUPPORTED with bsm_nd_factor_create's message, the
+ *    factor's bits untouched and the handle still valid. k == 0, empty
+ *    columns and stored zeros are no-ops. An update whose values overflow or
+ *    are not finite is found while it writes: BSM_ERR_UNSUPPORTED, and the
+ *    handle is left without values as after a failed refactor. Afterwards
+ *    *nnz_l is 0 again; the solves, logdet, the export, the selected inverse,
+ *    the refined and pcg solves and eigsh all see the new factor. The factor's
+ *    dtype, explicit fma, no atomics, a fixed order: the same call on the same
+ *    factor gives the same bits. Synchronous.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -537,6 +570,8 @@ int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_
 int bsm_dev_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev,
                                 uint64_t block, uint64_t ncv, double tol, uint64_t seed, const void* v0, double* lam,
                                 void* vecs, double* resid, uint32_t* info, void* stream);
+int bsm_nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                         const void* vals);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

@@ -836,6 +836,7 @@ public:
         detail::check(bsm_nd_factor_create(h.get(), &f));
         f_.reset(f);
         detail::check(bsm_nd_factor_info(f, &n_, nullptr, nullptr, nullptr));
+        src_dtype_ = detail::dtype_of<T>::value;
     }
 
     /// The factor in dtype T of a matrix of another float dtype
@@ -852,6 +853,7 @@ public:
         NdFactor out;
         out.f_.reset(f);
         detail::check(bsm_nd_factor_info(f, &out.n_, nullptr, nullptr, nullptr));
+        out.src_dtype_ = detail::dtype_of<U>::value;
         return out;
     }
 
@@ -871,6 +873,27 @@ public:
         auto h = a.device();
         detail::check(bsm_nd_factor_refactor(f_.get(), h.get()));
     }
+
+    /// The factor of P (S + W W^T) P^T in place (bsm_nd_factor_updown), S the
+    /// matrix this was the factor of, w of shape n x k, 1 <= k <= 16, of the
+    /// FACTORED MATRIX's dtype (another one throws std::invalid_argument,
+    /// another row count Panic). Only the fronts on the paths from w's columns
+    /// to the root are rewritten. A column is inside when, with its entry
+    /// that comes first in the new order (perm()) in tree node N, every other
+    /// entry is an own column or a front row of N: always so for alpha e_i and
+    /// for a vertex with any of its neighbours in S's graph that come later in
+    /// the new order (an edge of a stored (i, j)). A column outside, a row
+    /// >= n or k > 16 throws DeviceError before anything is written.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    void update(const Csr<U>& w) { updown(w, +1, "NdFactor::update"); }
+
+    /// The factor of P (S - W W^T) P^T in place: update's arguments and
+    /// errors. A w that leaves the matrix not positive definite throws
+    /// DeviceError; the factor keeps its bits and stays valid.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    void downdate(const Csr<U>& w) { updown(w, -1, "NdFactor::downdate"); }
 
     /// log det A = 2 sum log L_ii, summed in f64 in a fixed order.
     double logdet() const {
@@ -1078,11 +1101,33 @@ public:
 
 private:
     NdFactor() = default;
+    template <class U>
+    void updown(const Csr<U>& w, int sign, const char* what) {
+        if (w.get_dims().rows != n_) throw Panic(std::string(what) + ": IncorrectDimensions");
+        if (detail::dtype_of<U>::value != src_dtype_)
+            throw std::invalid_argument(std::string(what) + ": w must have the factored matrix's dtype");
+        // column-compressed: a counting sort by column keeps the rows ascending within each
+        const size_t k = w.get_dims().cols, nnz = w.v().size();
+        std::vector<uint64_t> cp(k + 1, 0), rows(nnz);
+        std::vector<U> vals(nnz);
+        for (size_t c : w.col_index()) ++cp[c + 1];
+        for (size_t c = 0; c < k; ++c) cp[c + 1] += cp[c];
+        std::vector<uint64_t> at(cp.begin(), cp.end() - 1);
+        const auto& rp = w.row_index();
+        for (size_t r = 0; r + 1 < rp.size(); ++r)
+            for (size_t e = rp[r]; e < rp[r + 1]; ++e) {
+                const uint64_t o = at[w.col_index()[e]]++;
+                rows[o] = r;
+                vals[o] = w.v()[e];
+            }
+        detail::check(bsm_nd_factor_updown(f_.get(), sign, k, cp.data(), rows.data(), vals.data()));
+    }
     struct Free {
         void operator()(bsm_nd_factor* p) const { bsm_nd_factor_free(p); }
     };
     std::unique_ptr<bsm_nd_factor, Free> f_;
     uint64_t n_ = 0;
+    int src_dtype_ = detail::dtype_of<T>::value;  // the factored matrix's dtype (update / downdate take W in it)
 };
 
 /// The nd factor of `a` computed and kept in dtype F (this build's addition):

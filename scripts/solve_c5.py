@@ -169,6 +169,9 @@ def main():
     ap.add_argument("--eig", type=int, default=0, metavar="NEV",
                     help="only the eigsh record: the NEV smallest eigenpairs on the kept factor, f64 and f32 factor, "
                          "block 4 and 8 (profiles/nd_eig_c5.jsonl)")
+    ap.add_argument("--updown", default=None, metavar="K[,K...]",
+                    help="only the update / downdate record: K random stored edges as one call, then the same call "
+                         "as a downdate, against refactor (profiles/nd_updown_c5.jsonl), for each K <= 16 given")
     ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
                     help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
                          "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
@@ -180,6 +183,15 @@ def main():
     rp, ci, v, b, x_true = system(g, dt)
     A = Csr.from_csr_arrays((n, n), rp, ci, v)
     B = Dense.from_columns([b])
+    if args.updown:
+        _lib.stage_timing(True)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "nd_updown_c5.jsonl"), "a") as out:
+            for line in nd_updown_ops(A, B, [int(k) for k in args.updown.split(",")], max(args.reps, 1),
+                                      (n, rp, ci, v)):
+                print(json.dumps(line), flush=True)
+                out.write(json.dumps(line) + "\n")
+        return
     if args.eig:
         _lib.stage_timing(True)
         print(json.dumps(nd_eig_ops(A, B, args.eig, max(args.reps, 1), g, args.mass)), flush=True)
@@ -535,6 +547,92 @@ def nd_pcg_ops(A, B, reps, pattern):
             "refined_converged": bool(ri.converged[0]), "refined_ms": med(t_ref), "tol": pi.tol,
         }
     return out
+
+
+def nd_updown_ops(A, B, ks, reps, pattern):
+    """The kept factor's rank-K update and downdate against refactor, f64: K
+    random stored edges (i, j) as one call, W's column sqrt(0.5) (e_i - e_j)
+    (half of the edge's conductance again, then taken out again), seeded. Host
+    wall ms around the synchronous C-ABI call on column-compressed arrays
+    built beforehand (medians of `reps`); python_ms is NdFactor.update on a
+    Csr of n rows, whose conversion to columns is host work over n. Stages by
+    mark: place (the work columns zeroed and W placed), sweep (a downdate's:
+    the dry pass and the writing pass), dinv. active_fronts: the union of the
+    K paths, from the host analysis. berr_after: the backward error of one
+    solve after the update and its downdate, against the factored matrix. One
+    JSON line per case, also appended to profiles/nd_updown_c5.jsonl."""
+    from basic_sparse_matrix_amd import cholesky_nd
+
+    n, rp, ci, v = pattern
+    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
+    cols = ci.astype(np.int64)
+    upper = np.flatnonzero(rows < cols)
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    lib = _lib.require_device()
+    lines = []
+    with cholesky_nd(A) as f:
+        perm = f.perm
+        pinv = np.empty(n, dtype=np.int64)
+        pinv[perm] = np.arange(n)
+        tree = solver.nd_analyse(n, rp, ci, leaf=int(os.environ.get("BSM_ND_LEAF", "192")))
+        assert np.array_equal(tree["perm"], perm)
+        owner = np.empty(n, dtype=np.int64)
+        for i, (a0, a1) in enumerate(zip(tree["start"], tree["end"])):
+            owner[a0:a1] = i
+        b0 = np.ascontiguousarray(B.get_col(0))
+        t_ref = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            f.refactor(A)
+            t_ref.append(time.perf_counter() - t0)
+        ref_stages = {k: round(t, 4) for k, t in _lib.stage_times().items()}
+        for K in ks:
+            pick = np.random.default_rng(1000 + K).choice(upper, size=K, replace=False)
+            cp = (2 * np.arange(K + 1)).astype(np.uint64)
+            wr = np.sort(np.stack([rows[pick], cols[pick]], axis=1), axis=1).astype(np.uint64).ravel()
+            wv = np.tile(np.array([np.sqrt(0.5), -np.sqrt(0.5)]), K)
+            active = set()
+            for e in pick:
+                x = int(owner[min(pinv[rows[e]], pinv[cols[e]])])
+                while x >= 0 and x not in active:
+                    active.add(x)
+                    x = int(tree["parent"][x])
+            wc = np.repeat(np.arange(K), 2)
+            o = np.lexsort((wc, wr.astype(np.int64)))
+            W = Csr.from_csr_arrays((n, K), np.concatenate([[0], np.cumsum(np.bincount(wr.astype(np.int64), minlength=n))])
+                                    .astype(np.uint64), wc[o].astype(np.uint64), wv[o])
+            times = {1: [], -1: []}
+            stages = {1: [], -1: []}
+            for _ in range(reps + 1):  # the first pair warms the temporaries
+                for sign in (1, -1):
+                    t0 = time.perf_counter()
+                    rc = lib.bsm_nd_factor_updown(f.handle, sign, K, _lib.ptr(cp), _lib.ptr(wr), _lib.ptr(wv))
+                    times[sign].append(time.perf_counter() - t0)
+                    assert rc == 0, _lib.last_error()
+                    stages[sign].append(_lib.stage_times())
+            x = np.asarray(f.solve(B).get_col(0), dtype=np.float64)
+            r = b0 - np.bincount(rows, weights=v * x[cols], minlength=n)
+            snorm = float(np.bincount(rows, weights=np.abs(v), minlength=n).max())
+            berr = float(np.abs(r).max() / (snorm * np.abs(x).max() + np.abs(b0).max()))
+            f.refactor(A)  # each K starts from the fresh factor
+            line = {"metric": "C5 nd factor: rank-K update and downdate of K stored edges against refactor "
+                              "(host wall ms, medians)",
+                    "config": {"g": int(round(n ** 0.5)), "K": int(K), "calls": reps, "dtype": "f64"},
+                    "active_fronts": len(active), "fronts": int(len(tree["start"])),
+                    "levels": int(tree["level"].max()) + 1, "refactor_ms": med(t_ref),
+                    "refactor_stages_ms": ref_stages, "berr_after": berr}
+            for sign, name in ((1, "update"), (-1, "downdate")):
+                line[name + "_ms"] = med(times[sign][1:])
+                line[name + "_ms_min_max"] = [round(1e3 * min(times[sign][1:]), 3), round(1e3 * max(times[sign][1:]), 3)]
+                line[name + "_stages_ms"] = {
+                    k: round(float(np.median([s_.get(k, 0.0) for s_ in stages[sign][1:]])), 4)
+                    for k in ("nd_updown_place", "nd_updown_sweep", "nd_updown_dinv")}
+            t0 = time.perf_counter()
+            f.update(W)
+            line["python_update_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+            f.refactor(A)
+            lines.append(line)
+    return lines
 
 
 def mass_matrix(g, kind):
