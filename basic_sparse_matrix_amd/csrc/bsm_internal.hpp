@@ -417,6 +417,15 @@ int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const 
 int nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, uint64_t nnz_w, const int64_t* colptr_dev,
                      const uint64_t* rows_dev, const void* vals_dev, uint64_t* n_miss, uint64_t* first_miss,
                      hipStream_t s);
+// A x = b for a sparse b, x at selected rows. b on the HOST,
+// column-compressed as nd_factor_updown's W and checked by the caller (col_ptr
+// ascending from 0, rows < n strictly ascending within a column), vals of f's
+// dtype; xrows: nq host rows < n, or null for every row. x_dev: ROW-major
+// nq x k (n x k) of f's dtype. info: 4 entries or null (bsm.h). The caller has
+// found n, k and the number of output rows positive. Synchronous on s.
+int nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                           const void* vals, uint64_t nq, const uint64_t* xrows, void* x_dev, uint32_t* info,
+                           hipStream_t s);
 // mixed precision on a kept factor (kernels_refine.hip)
 // n float values into the other float dtype, round-to-nearest (async on s)
 int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s);

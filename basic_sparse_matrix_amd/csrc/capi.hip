@@ -1454,6 +1454,89 @@ int bsm_nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, const uint64_t*
     return BSM_OK;
 }
 
+// solve_sparse's checks, bsm_nd_factor_updown's in its order; none asks for a device
+static int solve_sparse_check(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                              const void* vals, uint64_t nq, const uint64_t* xrows) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(k == 0 || col_ptr, BSM_ERR_INVALID, "null argument (col_ptr)");
+    BSM_REQUIRE(k == 0 || col_ptr[0] == 0, BSM_ERR_INVALID, "nd factor solve_sparse: col_ptr[0] must be 0, got %llu",
+                k ? (unsigned long long)col_ptr[0] : 0ull);
+    for (uint64_t c = 0; c < k; ++c) {
+        BSM_REQUIRE(col_ptr[c] <= col_ptr[c + 1], BSM_ERR_INVALID,
+                    "nd factor solve_sparse: col_ptr is not ascending at column %llu", (unsigned long long)c);
+        BSM_REQUIRE(col_ptr[c] == col_ptr[c + 1] || (rows && vals), BSM_ERR_INVALID, "null argument (rows or vals)");
+        for (uint64_t e = col_ptr[c] + 1; e < col_ptr[c + 1]; ++e)
+            BSM_REQUIRE(rows[e - 1] < rows[e], BSM_ERR_INVALID,
+                        "nd factor solve_sparse: rows must be strictly ascending within a column (column %llu, "
+                        "entries %llu and %llu are rows %llu and %llu)",
+                        (unsigned long long)c, (unsigned long long)(e - 1), (unsigned long long)e,
+                        (unsigned long long)rows[e - 1], (unsigned long long)rows[e]);
+    }
+    BSM_REQUIRE(nq == 0 || xrows, BSM_ERR_INVALID,
+                "nd factor solve_sparse: nq = %llu rows asked for but xrows is null (null with nq = 0: every row)",
+                (unsigned long long)nq);
+    const uint64_t nnz = k ? col_ptr[k] : 0;
+    for (uint64_t e = 0; e < nnz; ++e)
+        BSM_REQUIRE(rows[e] < f->n, BSM_ERR_OUT_OF_BOUNDS,
+                    "nd factor solve_sparse: entry %llu is row %llu, the matrix is %llu x %llu", (unsigned long long)e,
+                    (unsigned long long)rows[e], (unsigned long long)f->n, (unsigned long long)f->n);
+    for (uint64_t e = 0; e < nq; ++e)
+        BSM_REQUIRE(xrows[e] < f->n, BSM_ERR_OUT_OF_BOUNDS,
+                    "nd factor solve_sparse: requested row %llu is row %llu, the matrix is %llu x %llu",
+                    (unsigned long long)e, (unsigned long long)xrows[e], (unsigned long long)f->n,
+                    (unsigned long long)f->n);
+    return BSM_OK;
+}
+
+int bsm_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                               const void* vals, uint64_t nq, const uint64_t* xrows, void* const* x_cols,
+                               uint32_t* info) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    const uint64_t nout = xrows ? nq : f->n;
+    if (k > 0 && (xrows ? nq > 0 : nq == 0 && f->n > 0)) {  // x is written
+        BSM_REQUIRE(x_cols, BSM_ERR_INVALID, "null argument (x_cols)");
+        for (uint64_t j = 0; j < k; ++j)
+            BSM_REQUIRE(x_cols[j], BSM_ERR_INVALID, "null column pointer %llu (x)", (unsigned long long)j);
+    }
+    BSM_TRY(solve_sparse_check(f, k, col_ptr, rows, vals, nq, xrows));
+    if (k == 0) return BSM_OK;
+    if (nout == 0) {  // nothing asked for: no pass runs
+        for (int i = 0; i < 4 && info; ++i) info[i] = 0;
+        return BSM_OK;
+    }
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    DBuf x;
+    BSM_TRY(x.alloc((size_t)nout * k * dtype_size(f->dtype)));
+    uint32_t inf[4] = {0, 0, 0, 0};
+    BSM_TRY(nd_factor_solve_sparse(f, k, col_ptr, rows, vals, nq, xrows, x.p, inf, s));
+    BSM_TRY(download_columns(f->dtype, nout, k, x.p, x_cols, s));
+    for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                                   const void* vals, uint64_t nq, const uint64_t* xrows, void* x, uint32_t* info,
+                                   void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    const uint64_t nout = xrows ? nq : f->n;
+    BSM_REQUIRE(!(k > 0 && (xrows ? nq > 0 : nq == 0 && f->n > 0)) || x, BSM_ERR_INVALID, "null argument (x)");
+    BSM_TRY(solve_sparse_check(f, k, col_ptr, rows, vals, nq, xrows));
+    if (k == 0) return BSM_OK;
+    if (nout == 0) {
+        for (int i = 0; i < 4 && info; ++i) info[i] = 0;
+        return BSM_OK;
+    }
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    uint32_t inf[4] = {0, 0, 0, 0};
+    BSM_TRY(nd_factor_solve_sparse(f, k, col_ptr, rows, vals, nq, xrows, x, inf, static_cast<hipStream_t>(stream)));
+    for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
+    return BSM_OK;
+}
+
 int bsm_nd_factor_info(const bsm_nd_factor* f, uint64_t* n, int* dtype, uint64_t* bytes, uint64_t* nnz_l) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
     std::lock_guard<std::mutex> lk(f->mu);

@@ -34,6 +34,7 @@
 
 #include "bsm_internal.hpp"
 #include "nd.hpp"
+#include "reach_rule.hpp"
 #include "updown_rule.hpp"
 
 namespace bsm {
@@ -651,16 +652,19 @@ __global__ __launch_bounds__(256) void nd_y_in(const NdDev* __restrict__ nodes, 
 // written write-through (rows change hands between threads). Every product's
 // loads are issued together (unrolled): a loop of load, wait, FMA is one
 // L2 round trip per term, 64 per tile step.
+// The body is nd_forward_front: nd_forward runs it on every front of a level
+// with both children, nd_forward_path (the sparse right-hand sides, §4.9k) on
+// the active fronts alone with their ACTIVE children (kids: bit 0 = kid0,
+// bit 1 = kid1; an inactive child's update vector would be +0 and its V is
+// never written).
 template <typename T>
-__global__ __launch_bounds__(256, 4) void nd_forward(const NdDev* __restrict__ nodes, const int32_t* __restrict__ lvl,
-                                                  int64_t n, const T* __restrict__ bp, T* __restrict__ V, int64_t vtot,
-                                                  const T* __restrict__ F, const T* __restrict__ Dinv,
-                                                  const int32_t* __restrict__ ri) {
+__device__ __forceinline__ void nd_forward_front(const NdDev* __restrict__ nodes, const NdDev& nd, int kids,
+                                                 int64_t col, int64_t n, const T* __restrict__ bp, T* __restrict__ V,
+                                                 int64_t vtot, const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                 const int32_t* __restrict__ ri) {
     __shared__ T vk[64], yk[64];
     __shared__ T part[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const NdDev& nd = nodes[lvl[blockIdx.x]];
-    const int64_t col = blockIdx.y;
     T* const v = V + col * vtot + nd.voff;
     const int fp = 64 * nd.nt;
     for (int r = tid; r < fp; r += 256) st_sc1(&v[r], r < nd.np ? bp[col * n + nd.start + r] : (T)0);
@@ -669,7 +673,7 @@ __global__ __launch_bounds__(256, 4) void nd_forward(const NdDev* __restrict__ n
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int kid = s == 0 ? nd.kid0 : nd.kid1;
-        if (kid < 0) continue;
+        if (kid < 0 || !((kids >> s) & 1)) continue;
         const NdDev& c = nodes[kid];
         const T* u = V + col * vtot + c.voff + c.np_pad;
         const int32_t* rc = ri + c.st_off;
@@ -736,6 +740,25 @@ __global__ __launch_bounds__(256, 4) void nd_forward(const NdDev* __restrict__ n
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 4) void nd_forward(const NdDev* __restrict__ nodes, const int32_t* __restrict__ lvl,
+                                                  int64_t n, const T* __restrict__ bp, T* __restrict__ V, int64_t vtot,
+                                                  const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                  const int32_t* __restrict__ ri) {
+    nd_forward_front<T>(nodes, nodes[lvl[blockIdx.x]], 3, blockIdx.y, n, bp, V, vtot, F, Dinv, ri);
+}
+
+// one workgroup per (active front, column); act: the level's part of the forward set
+template <typename T>
+__global__ __launch_bounds__(256, 4) void nd_forward_path(const NdDev* __restrict__ nodes,
+                                                       const ReachFront* __restrict__ act, int64_t n,
+                                                       const T* __restrict__ bp, T* __restrict__ V, int64_t vtot,
+                                                       const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                       const int32_t* __restrict__ ri) {
+    const ReachFront me = act[blockIdx.x];
+    nd_forward_front<T>(nodes, nodes[me.node], me.kids, blockIdx.y, n, bp, V, vtot, F, Dinv, ri);
 }
 
 // A solve wave waits on a pivot tile of its own front that a running wave
@@ -874,19 +897,26 @@ __global__ __launch_bounds__(64) void nd_forward_tiles(const NdDev* __restrict__
 // Backward solve of one level, one workgroup per (node, column): w = y over
 // the pivots, the ancestors' x over the front rows; per pivot tile K from the
 // last, x_K = Dinv_K^T (y_K - L_{>K,K}^T w_{>K}); the pivots' x to xp.
+// The body is nd_backward_front: nd_backward runs it on every front of a
+// level, nd_backward_path (§4.9k) on the fronts on the paths from the requested
+// rows to the root. has_y: the forward pass has left y over the pivots (and 0
+// over the padding pivots and the rows past f); else the front was not
+// forward-active, y = 0, and those rows are written as 0 here (V may hold
+// anything there).
 template <typename T>
-__global__ __launch_bounds__(256) void nd_backward(const NdDev* __restrict__ nodes, const int32_t* __restrict__ lvl,
-                                                   int64_t n, T* __restrict__ xp, T* __restrict__ V, int64_t vtot,
-                                                   const T* __restrict__ F, const T* __restrict__ Dinv,
-                                                   const int32_t* __restrict__ st) {
+__device__ __forceinline__ void nd_backward_front(const NdDev& nd, bool has_y, int64_t col, int64_t n,
+                                                  T* __restrict__ xp, T* __restrict__ V, int64_t vtot,
+                                                  const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                  const int32_t* __restrict__ st) {
     __shared__ T red[64][65];
     __shared__ T zk[64];
     __shared__ T part[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const NdDev& nd = nodes[lvl[blockIdx.x]];
-    const int64_t col = blockIdx.y;
     T* const w = V + col * vtot + nd.voff;
     const int fp = 64 * nd.nt;
+    if (!has_y)  // every row but the front rows (written next, by other threads)
+        for (int r = tid; r < fp; r += 256)
+            if (r < nd.np_pad || r >= nd.np_pad + nd.m) st_sc1(&w[r], (T)0);
     for (int a = tid; a < nd.m; a += 256) st_sc1(&w[nd.np_pad + a], xp[col * n + st[nd.st_off + a]]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -962,6 +992,26 @@ __global__ __launch_bounds__(256) void nd_backward(const NdDev* __restrict__ nod
         __syncthreads();
     }
     for (int p = tid; p < nd.np; p += 256) xp[col * n + nd.start + p] = ld_sc1(&w[p]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void nd_backward(const NdDev* __restrict__ nodes, const int32_t* __restrict__ lvl,
+                                                   int64_t n, T* __restrict__ xp, T* __restrict__ V, int64_t vtot,
+                                                   const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                   const int32_t* __restrict__ st) {
+    nd_backward_front<T>(nodes[lvl[blockIdx.x]], true, blockIdx.y, n, xp, V, vtot, F, Dinv, st);
+}
+
+// one workgroup per (active front, column); act: the level's part of the
+// backward set, kids != 0: the front was forward-active too
+template <typename T>
+__global__ __launch_bounds__(256) void nd_backward_path(const NdDev* __restrict__ nodes,
+                                                        const ReachFront* __restrict__ act, int64_t n,
+                                                        T* __restrict__ xp, T* __restrict__ V, int64_t vtot,
+                                                        const T* __restrict__ F, const T* __restrict__ Dinv,
+                                                        const int32_t* __restrict__ st) {
+    const ReachFront me = act[blockIdx.x];
+    nd_backward_front<T>(nodes[me.node], me.kids != 0, blockIdx.y, n, xp, V, vtot, F, Dinv, st);
 }
 
 // Backward solve of one level by pivot tiles: one workgroup per (node, pivot
@@ -1101,6 +1151,7 @@ struct NdLayout {
     std::vector<int2> btasks;                  // nd_backward_tiles' (node, pivot tile), last tiles first
     std::vector<int64_t> btask_off;            // per level
     std::vector<int32_t> parent, level;        // per node, for the host (NdCached::h_parent / h_level)
+    std::vector<int32_t> kid0, kid1;           // likewise (NdCached::h_kid0 / h_kid1)
     int64_t f_elems = 0, dinv_elems = 0, n_flags = 0, vtot = 0, n_lower = 0;
 };
 
@@ -1116,6 +1167,8 @@ void nd_layout(const NdPlan& P, NdLay lay, NdLayout& L) {
     L.dev.resize((size_t)nn);
     L.parent.resize((size_t)nn);
     L.level.resize((size_t)nn);
+    L.kid0.resize((size_t)nn);
+    L.kid1.resize((size_t)nn);
     int64_t st_total = 0;
     for (int32_t i = 0; i < nn; ++i) {
         const NdNode& x = P.nodes[(size_t)i];
@@ -1132,6 +1185,8 @@ void nd_layout(const NdPlan& P, NdLay lay, NdLayout& L) {
         L.level[(size_t)i] = x.level;
         d.kid0 = x.kids[0];
         d.kid1 = x.kids[1];
+        L.kid0[(size_t)i] = x.kids[0];
+        L.kid1[(size_t)i] = x.kids[1];
         d.tb_off = -1;
         d.tile_off = (int32_t)L.n_lower;
         L.n_lower += (int64_t)d.nt * (d.nt + 1) / 2;
@@ -1343,6 +1398,8 @@ struct NdCached {
     // each node's parent and level on the host: the update / downdate of a kept
     // factor builds its active fronts' per-level lists from them (§4.9j)
     std::vector<int32_t> h_parent, h_level;
+    // and its two children: the sparse solve's forward set names the active ones (§4.9k)
+    std::vector<int32_t> h_kid0, h_kid1;
     DBuf aent, tq;                    // the default pipeline: A's entries by tile (nd_aent_*), per task ranges
     DBuf pdesc;                       // and per task its children's blocks (nd_task_pull)
     NdLay lay;
@@ -1631,6 +1688,8 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, NdLay lay, int threads, size_t
     C.btask_off = L.btask_off;
     C.h_parent = std::move(L.parent);
     C.h_level = std::move(L.level);
+    C.h_kid0 = std::move(L.kid0);
+    C.h_kid1 = std::move(L.kid1);
     C.f_elems = L.f_elems;
     C.dinv_elems = L.dinv_elems;
     C.n_flags = L.n_flags;
@@ -2087,6 +2146,33 @@ int nd_factor_levels(const NdCached& C, const NdGrid& g, T* F, T* Dinv, int* fla
     return BSM_OK;
 }
 
+// The backward levels of a solve, top-down over every front: y over each
+// front's pivots in V, x into bp. d_xf / d_btk: the pass's cleared flags (one
+// per node, column and pivot tile) and tickets (one per level). Levels with
+// fewer (node, column) pairs than CUs run by tiles (nd_solve_passes).
+template <typename T>
+int nd_backward_levels(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
+                       const T* Dinv, T* bp, T* V, int* d_xf, int* d_btk, int* d_status, hipStream_t s) {
+    const NdPtrs p = nd_ptrs(C);
+    const int64_t bwd_grid = (int64_t)g.cus * g.bper;
+    for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
+        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
+        if (c <= 0) continue;
+        if (opt.bwd_tiles == 1 || (opt.bwd_tiles == 2 && c * (int64_t)k < g.cus)) {
+            const int64_t b0 = C.btask_off[(size_t)lv], nb = C.btask_off[(size_t)lv + 1] - b0;
+            const int64_t grid = std::min<int64_t>(nb * (int64_t)k, bwd_grid);
+            if (grid <= 0) continue;  // no pivots on this level
+            nd_backward_tiles<T><<<(unsigned)grid, 256, 0, s>>>(p.nodes, p.btask + b0, nb, (int)k, N, bp, V, C.vtot, F,
+                                                                Dinv, p.st, d_xf, d_btk + lv, d_status);
+        } else {
+            nd_backward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
+                                                                         p.st);
+        }
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    return BSM_OK;
+}
+
 // The solves on a finished factor (F, Dinv): b into the new order, the
 // forward levels bottom-up, the backward levels top-down, x back into A's
 // order. folded: nd_factor has formed the forward solve already (t.bpb and
@@ -2121,7 +2207,7 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
     int* const d_xf = d_yf + t.n_pf;
     int* const d_ftk = d_xf + t.n_pf;
     int* const d_btk = d_ftk + C.n_levels;
-    const int64_t fwd_grid = (int64_t)cus * g.fper, bwd_grid = (int64_t)cus * g.bper;
+    const int64_t fwd_grid = (int64_t)cus * g.fper;
     for (int32_t lv = 0; lv < C.n_levels && fwd; ++lv) {
         const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
         if (c <= 0) continue;
@@ -2146,21 +2232,7 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
         nd_y_in<T><<<dim3((unsigned)C.nn, (unsigned)k), 256, 0, s>>>(p.nodes, N, bp, V, C.vtot);
         BSM_HIP_TRY(hipGetLastError());
     }
-    for (int32_t lv = C.n_levels - 1; lv >= 0 && bwd; --lv) {
-        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
-        if (c <= 0) continue;
-        if (by_tiles(opt.bwd_tiles, c * (int64_t)k)) {
-            const int64_t b0 = C.btask_off[(size_t)lv], nb = C.btask_off[(size_t)lv + 1] - b0;
-            const int64_t grid = std::min<int64_t>(nb * (int64_t)k, bwd_grid);
-            if (grid <= 0) continue;  // no pivots on this level
-            nd_backward_tiles<T><<<(unsigned)grid, 256, 0, s>>>(p.nodes, p.btask + b0, nb, (int)k, N, bp, V, C.vtot, F,
-                                                                Dinv, p.st, d_xf, d_btk + lv, d_status);
-        } else {
-            nd_backward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
-                                                                         p.st);
-        }
-        BSM_HIP_TRY(hipGetLastError());
-    }
+    if (bwd) BSM_TRY(nd_backward_levels<T>(C, opt, g, N, k, F, Dinv, bp, V, d_xf, d_btk, d_status, s));
     stage_mark("nd_backward", s);
     nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, perm, bp, static_cast<T*>(x_dev));
     BSM_HIP_TRY(hipGetLastError());
@@ -3374,7 +3446,205 @@ int nd_factor_updown_t(bsm_nd_factor& f, int sign, int k, const int64_t* colptr_
     return BSM_OK;
 }
 
+// ---- sparse right-hand sides and selected solution rows -----
+// A x = b for a column-compressed b, x wanted at some rows: the forward pass on
+// the fronts on the paths from b's entries to the root, the backward pass on
+// those from the requested rows' fronts (reach_rule.hpp), per level over the
+// active fronts alone (nd_forward_path / nd_backward_path: nd_forward's and
+// nd_backward's own bodies). Every value returned goes through the operations
+// of the dense solve in its order: the same bits, but for a -0 that a skipped
+// +0 addition leaves. No flags, no tickets: every dependency is a launch
+// boundary or a __syncthreads. Columns go in chunks of ND_SPARSE_CHUNK, so bp
+// and V are the dense solve's of that many columns. With rows requested V is
+// never cleared (the fronts that are not active are neither read nor
+// written); with every row wanted the dense solve's own backward levels run
+// on all fronts, over a V cleared first (y = 0 off the forward set).
+
+constexpr uint64_t ND_SPARSE_CHUNK = 32;
+
+// own[i] = the front owning row rows[i] (A's order, < n)
+__global__ __launch_bounds__(256) void nd_sparse_owners(int64_t cnt, const uint64_t* __restrict__ rows,
+                                                        const int32_t* __restrict__ pinv,
+                                                        const int32_t* __restrict__ owner, int32_t* __restrict__ own) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) own[i] = owner[pinv[rows[i]]];
+}
+
+// Place, first half: what nd_forward_path reads of bp, the pivots of the
+// forward-active fronts, cleared. One workgroup per (active front, column).
+template <typename T>
+__global__ __launch_bounds__(256) void nd_sparse_clear(const NdDev* __restrict__ nodes,
+                                                       const ReachFront* __restrict__ act, int64_t n,
+                                                       T* __restrict__ bp) {
+    const NdDev& nd = nodes[act[blockIdx.x].node];
+    T* const d = bp + (int64_t)blockIdx.y * n + nd.start;
+    for (int r = threadIdx.x; r < nd.np; r += 256) d[r] = (T)0;
+}
+
+// Place, second half (after a launch boundary): column c0 + blockIdx.x of b
+// into column blockIdx.x of bp, in the new order. Rows are strictly ascending
+// within a column: no two entries meet.
+template <typename T>
+__global__ __launch_bounds__(64) void nd_sparse_place(const int64_t* __restrict__ colptr,
+                                                      const uint64_t* __restrict__ rows, const T* __restrict__ vals,
+                                                      const int32_t* __restrict__ pinv, int64_t n, int64_t c0,
+                                                      T* __restrict__ bp) {
+    const int64_t col = c0 + blockIdx.x;
+    T* const d = bp + (int64_t)blockIdx.x * n;
+    for (int64_t e = colptr[col] + threadIdx.x; e < colptr[col + 1]; e += 64) d[pinv[rows[e]]] = vals[e];
+}
+
+// x[e][c0 + c] = x_c at row xrows[e] (xrows == null: row e) for the chunk's kc
+// columns; x row-major with ldx columns
+template <typename T>
+__global__ __launch_bounds__(256) void nd_sparse_gather(int64_t nout, const uint64_t* __restrict__ xrows,
+                                                        const int32_t* __restrict__ pinv, int64_t n, int kc,
+                                                        const T* __restrict__ bp, T* __restrict__ x, int64_t ldx,
+                                                        int64_t c0) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nout) return;
+    const int64_t q = pinv[xrows ? (int64_t)xrows[e] : e];
+    for (int c = 0; c < kc; ++c) x[e * ldx + c0 + c] = bp[(int64_t)c * n + q];
+}
+
+// The caller holds f.mu and has found f valid and every index < n. b on the
+// host (col_ptr k + 1, rows and vals col_ptr[k]); xrows: nq rows on the host,
+// or null for every row. x_dev: ROW-major nq x k (n x k).
+template <typename T>
+int nd_factor_solve_sparse_t(const bsm_nd_factor& f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                             const void* vals, uint64_t nq, const uint64_t* xrows, void* x_dev, uint32_t* info,
+                             hipStream_t s) {
+    stage_reset(s);
+    const int64_t N = (int64_t)f.n;
+    const NdOpts opt = nd_options();
+    const NdCached& C = *std::static_pointer_cast<NdCached>(f.plan);
+    const NdPtrs p = nd_ptrs(C);
+    const bool all = xrows == nullptr;
+    const uint64_t nnz = col_ptr[k], nout = all ? (uint64_t)N : nq, nidx = nnz + nq;
+    const uint64_t kc_max = std::min<uint64_t>(k, ND_SPARSE_CHUNK), chunks = (k + ND_SPARSE_CHUNK - 1) / ND_SPARSE_CHUNK;
+    // everything that can fail before the first launch
+    NdGrid g;
+    if (all) BSM_TRY(nd_grid<T>(false, true, g));
+    DBuf cpb, idxb, valb, ownb, bpb, vb, tfl;
+    BSM_TRY(cpb.alloc((size_t)(k + 1) * 8, s));
+    BSM_TRY(idxb.alloc((size_t)nidx * 8, s));
+    BSM_TRY(valb.alloc((size_t)nnz * sizeof(T), s));
+    BSM_TRY(ownb.alloc((size_t)nidx * sizeof(int32_t), s));
+    const size_t bp_b = (size_t)N * kc_max * sizeof(T), v_b = (size_t)std::max<int64_t>(C.vtot, 1) * kc_max * sizeof(T);
+    BSM_TRY(bpb.alloc(bp_b, s));
+    BSM_TRY(vb.alloc(v_b, s));
+    // every front's backward pass (the dense solve's levels): its flags, tickets and status word
+    const int64_t n_pf = (C.dinv_elems / 4096) * (int64_t)kc_max;
+    const size_t n_tf = (size_t)n_pf + (size_t)C.n_levels;
+    if (all) BSM_TRY(tfl.alloc((n_tf + 1) * sizeof(int), s));
+    NdDrainOnError drain{s};  // the handle's mutex is released after this guard runs
+    drain.armed = true;
+    uint64_t* const d_idx = idxb.as<uint64_t>();
+    BSM_TRY(h2d_staged(cpb.p, col_ptr, (size_t)(k + 1) * 8, s));
+    if (nnz) {
+        BSM_TRY(h2d_staged(d_idx, rows, (size_t)nnz * 8, s));
+        BSM_TRY(h2d_staged(valb.p, vals, (size_t)nnz * sizeof(T), s));
+    }
+    if (nq) BSM_TRY(h2d_staged(d_idx + nnz, xrows, (size_t)nq * 8, s));
+    // the owners of b's rows and of the requested rows, copied back once
+    std::vector<int32_t> own((size_t)nidx);
+    if (nidx) {
+        nd_sparse_owners<<<nd_blocks((int64_t)nidx, 256), 256, 0, s>>>((int64_t)nidx, d_idx, p.pinv, p.owner,
+                                                                         ownb.as<int32_t>());
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_HIP_TRY(read_dev(own.data(), ownb.p, (size_t)nidx * sizeof(int32_t), s));
+    }
+    stage_mark("nd_sparse_owners", s);
+    const size_t nn = (size_t)C.nn;
+    std::vector<unsigned char> fmark, bmark;
+    ReachSet fw, bw;
+    reach_set(nn, C.h_parent.data(), C.h_level.data(), C.h_kid0.data(), C.h_kid1.data(), own.data(), (size_t)nnz, fmark,
+              fw);
+    if (!all) {
+        reach_set(nn, C.h_parent.data(), C.h_level.data(), nullptr, nullptr, own.data() + nnz, (size_t)nq, bmark, bw);
+        for (ReachFront& b : bw.fronts) b.kids = fmark[(size_t)b.node];  // y from the forward pass, else 0
+    }
+    const size_t nf = fw.fronts.size(), nb = bw.fronts.size();
+    DBuf actb;
+    BSM_TRY(actb.alloc((nf + nb) * sizeof(ReachFront), s));
+    const ReachFront* const d_fw = actb.as<ReachFront>();
+    const ReachFront* const d_bw = d_fw + nf;
+    if (nf) BSM_TRY(h2d_staged(actb.p, fw.fronts.data(), nf * sizeof(ReachFront), s));
+    if (nb) BSM_TRY(h2d_staged(actb.as<ReachFront>() + nf, bw.fronts.data(), nb * sizeof(ReachFront), s));
+    T* const bp = bpb.as<T>();
+    T* const V = vb.as<T>();
+    const T* const F = f.fr.as<T>();
+    const T* const Dinv = f.dv.as<T>();
+    int* const d_status = all ? tfl.as<int>() + n_tf : nullptr;
+    for (uint64_t c0 = 0; c0 < k; c0 += ND_SPARSE_CHUNK) {
+        const unsigned kc = (unsigned)std::min<uint64_t>(ND_SPARSE_CHUNK, k - c0);
+        // BSM_ND_POISON=1 (tests): nothing the passes did not write may be read
+        if (opt.poison) {
+            BSM_HIP_TRY(hipMemsetAsync(bpb.p, 0xff, bp_b, s));
+            BSM_HIP_TRY(hipMemsetAsync(vb.p, 0xff, v_b, s));
+        }
+        if (all) {  // the dense backward levels read y of every front: 0 where the forward pass does not run
+            BSM_HIP_TRY(hipMemsetAsync(vb.p, 0, (size_t)std::max<int64_t>(C.vtot, 1) * kc * sizeof(T), s));
+            BSM_HIP_TRY(hipMemsetAsync(tfl.p, 0, (n_tf + 1) * sizeof(int), s));
+        }
+        if (nf) {
+            nd_sparse_clear<T><<<dim3((unsigned)nf, kc), 256, 0, s>>>(p.nodes, d_fw, N, bp);
+            BSM_HIP_TRY(hipGetLastError());
+            nd_sparse_place<T><<<kc, 64, 0, s>>>(cpb.as<int64_t>(), d_idx, valb.as<T>(), p.pinv, N, (int64_t)c0, bp);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        for (size_t li = 0; li < fw.levels.size(); ++li) {
+            const int32_t a0 = fw.first(li), cnt = fw.last(li) - a0;
+            nd_forward_path<T><<<dim3((unsigned)cnt, kc), 256, 0, s>>>(p.nodes, d_fw + a0, N, bp, V, C.vtot, F, Dinv,
+                                                                      p.ri);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+        stage_mark("nd_sparse_forward", s);
+        if (all) {
+            BSM_TRY(nd_backward_levels<T>(C, opt, g, N, kc, F, Dinv, bp, V, tfl.as<int>(), tfl.as<int>() + n_pf,
+                                          d_status, s));
+        } else {
+            for (size_t li = bw.levels.size(); li-- > 0;) {
+                const int32_t a0 = bw.first(li), cnt = bw.last(li) - a0;
+                nd_backward_path<T><<<dim3((unsigned)cnt, kc), 256, 0, s>>>(p.nodes, d_bw + a0, N, bp, V, C.vtot, F,
+                                                                           Dinv, p.st);
+                BSM_HIP_TRY(hipGetLastError());
+            }
+        }
+        stage_mark("nd_sparse_backward", s);
+        if (nout) {
+            nd_sparse_gather<T><<<nd_blocks((int64_t)nout, 256), 256, 0, s>>>(
+                (int64_t)nout, all ? nullptr : d_idx + nnz, p.pinv, N, (int)kc, bp, static_cast<T*>(x_dev), (int64_t)k,
+                (int64_t)c0);
+            BSM_HIP_TRY(hipGetLastError());
+        }
+    }
+    int h = 0;
+    if (all) BSM_HIP_TRY(read_dev(&h, d_status, sizeof(int), s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    stage_mark("nd_sparse_gather", s);
+    BSM_REQUIRE(!(h & ST_TIMEOUT), BSM_ERR_HIP, "nd solve: tile hand-off timed out");
+    if (info) {
+        info[0] = (uint32_t)nf;
+        info[1] = (uint32_t)(all ? nn : nb);
+        info[2] = (uint32_t)nn;
+        info[3] = (uint32_t)chunks;
+    }
+    return BSM_OK;
+}
+
 }  // namespace
+
+int nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                           const void* vals, uint64_t nq, const uint64_t* xrows, void* x_dev, uint32_t* info,
+                           hipStream_t s) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    BSM_REQUIRE(f->valid, BSM_ERR_INVALID, "nd factor: factor holds no values; refactor first");
+    return f->dtype == BSM_F64
+               ? nd_factor_solve_sparse_t<double>(*f, k, col_ptr, rows, vals, nq, xrows, x_dev, info, s)
+               : nd_factor_solve_sparse_t<float>(*f, k, col_ptr, rows, vals, nq, xrows, x_dev, info, s);
+}
 
 int nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, uint64_t nnz_w, const int64_t* colptr_dev,
                      const uint64_t* rows_dev, const void* vals_dev, uint64_t* n_miss, uint64_t* first_miss,

@@ -199,6 +199,47 @@ def nd_factor_solve(factor, b: torch.Tensor, out: torch.Tensor | None = None, *,
     return out
 
 
+def nd_factor_solve_sparse(factor, b, rows=None, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
+    """``NdFactor.solve_sparse`` with ``x`` resident in HBM
+    (``bsm_dev_nd_factor_solve_sparse``): ``b`` is a host ``Csr`` of shape
+    ``n x k`` of the factor's dtype, ``rows`` a 1-D integer array-like or
+    ``None`` (every row), both as ``NdFactor.solve_sparse`` takes them; ``out``
+    is row-major ``(len(rows), k)`` (``(n, k)``), contiguous, of the factor's
+    dtype, on its device, and defaults to a new tensor. Runs on ``stream`` and
+    returns after it has drained; the same kernels and bits as the host call."""
+    from .solver import MatErr, MatErrKind, NdFactor
+    from .sparse import _raise_for
+
+    h = factor._h()
+    if b.dims.rows != factor.n:
+        raise MatErr(MatErrKind.IncorrectDimensions)
+    if b.dtype != factor.dtype:
+        raise TypeError(f"nd_factor_solve_sparse: needs Csr<{factor.dtype}> (the factor's dtype), got {b.dtype}")
+    r = None if rows is None else NdFactor._rows_arg("solve_sparse", "rows", rows)
+    k = b.dims.cols
+    nout = factor.n if r is None else r.shape[0]
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    out = torch.empty((nout, k), dtype=want, device="cuda") if out is None else out
+    if out.dtype != want:
+        raise TypeError(f"nd_factor_solve_sparse: out is {out.dtype}, the factor is {factor.dtype}")
+    if not out.is_cuda:
+        raise ValueError("nd_factor_solve_sparse: out is not on the device")
+    if tuple(out.shape) != (nout, k) or not out.is_contiguous():
+        raise ValueError(f"nd_factor_solve_sparse: out must be contiguous, ({nout}, {k}), got {tuple(out.shape)}")
+    rp, ci, v = b._csr_arrays()
+    b_rows = np.repeat(np.arange(factor.n, dtype=np.uint64), np.diff(np.asarray(rp).astype(np.int64)))
+    cols = np.asarray(ci).astype(np.int64)
+    order = np.argsort(cols, kind="stable")  # column-compressed: rows stay ascending within a column
+    col_ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=k))]).astype(np.uint64)
+    br = np.ascontiguousarray(b_rows[order])
+    vals = np.ascontiguousarray(np.asarray(v, dtype=factor.dtype)[order])
+    if k and nout:  # an empty ``rows`` would read as NULL ("every row") on the other side
+        _raise_for(_lib.require_device().bsm_dev_nd_factor_solve_sparse(
+            h, k, _lib.ptr(col_ptr), _lib.ptr(br), _lib.ptr(vals), 0 if r is None else nout,
+            None if r is None else _lib.ptr(r), _p(out), None, _stream(stream)))
+    return out
+
+
 def nd_factor_solve_refined(factor, a, b: torch.Tensor, out: torch.Tensor | None = None, *, max_iter: int = 5,
                             tol: float | None = None, stream=None):
     """``NdFactor.solve_refined`` with ``b`` and ``x`` resident in HBM

@@ -513,6 +513,87 @@ class NdFactor:
         writes only scratch: the factor keeps its bits and stays valid."""
         self._updown(w, -1, "downdate")
 
+    @staticmethod
+    def _rows_arg(what: str, name: str, x) -> np.ndarray:
+        r = np.asarray(x)
+        if r.ndim != 1:
+            raise ValueError(f"NdFactor.{what}: {name} must be 1-D, got {r.shape}")
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise TypeError(f"NdFactor.{what}: {name} must be integers, got {r.dtype}")
+        if r.size and int(r.min()) < 0:
+            raise ValueError(f"NdFactor.{what}: {name} has a negative index")
+        return np.ascontiguousarray(r, dtype=np.uint64)
+
+    def _solve_sparse(self, k: int, col_ptr, b_rows, vals, rows):
+        """``bsm_nd_factor_solve_sparse``: (the k result columns, info)."""
+        h = self._h()
+        nout = self.n if rows is None else rows.shape[0]
+        cols = [np.zeros(nout, dtype=self.dtype) for _ in range(k)]
+        info = np.zeros(4, dtype=np.uint32)
+        if k and nout:  # an empty ``rows`` would read as NULL ("every row") on the other side
+            lib = _lib.require_device()
+            _raise_for(lib.bsm_nd_factor_solve_sparse(h, k, _lib.ptr(col_ptr), _lib.ptr(b_rows), _lib.ptr(vals),
+                                                      0 if rows is None else nout,
+                                                      None if rows is None else _lib.ptr(rows),
+                                                      _lib.ptr_array(cols), _lib.ptr(info)))
+        return cols, tuple(int(v) for v in info)
+
+    def solve_sparse(self, b: Csr, rows=None, *, info: bool = False):
+        """``x = A^-1 b`` for a SPARSE ``b`` (``bsm_nd_factor_solve_sparse``),
+        with ``x`` wanted at ``rows`` only: a Green's function between two
+        points, an effective resistance, a covariance ``(A^-1)[i, j]`` off the
+        pattern of ``L + L^T``. ``b`` is a ``Csr`` of shape ``n x k`` of the
+        FACTOR's dtype (else ``TypeError``; another row count raises
+        ``MatErr(IncorrectDimensions)``); ``rows`` a 1-D integer array-like
+        (A's order, unsorted and repeated as you like; not 1-D or negative:
+        ``ValueError``, not integers: ``TypeError``, ``>= n``:
+        ``MatErr(OutOfBounds)``), or ``None`` for every row. Returns a
+        ``Dense`` of shape ``len(rows) x k`` (``n x k``): row ``e`` is
+        ``x[rows[e]]``.
+
+        Only the fronts on the paths from ``b``'s entries to the root of the
+        separator tree run the forward pass and only those from the fronts
+        owning ``rows`` the backward pass (15 and 14 of 15,397 at C5 for a point
+        source and one row), with the dense solve's operations in its order:
+        every value EQUALS ``solve``'s on the densified ``b`` (``np.array_equal``;
+        a zero may differ in sign), whatever else is asked for in the same
+        call. Stored zeros are ordinary entries, an empty column gives a zero
+        column. ``info=True`` returns ``(x, (forward fronts, backward fronts,
+        fronts in the plan, column chunks))``."""
+        self._h()
+        if b.dims.rows != self.n:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        if b.dtype != self.dtype:
+            raise TypeError(f"NdFactor.solve_sparse: needs Csr<{self.dtype}> (the factor's dtype), got {b.dtype}")
+        r = None if rows is None else self._rows_arg("solve_sparse", "rows", rows)
+        k = b.dims.cols
+        rp, ci, v = b._csr_arrays()
+        b_rows = np.repeat(np.arange(self.n, dtype=np.uint64), np.diff(np.asarray(rp).astype(np.int64)))
+        cols = np.asarray(ci).astype(np.int64)
+        order = np.argsort(cols, kind="stable")  # column-compressed: rows stay ascending within a column
+        col_ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=k))]).astype(np.uint64)
+        out, inf = self._solve_sparse(k, col_ptr, np.ascontiguousarray(b_rows[order]),
+                                      np.ascontiguousarray(np.asarray(v, dtype=self.dtype)[order]), r)
+        nout = self.n if r is None else r.shape[0]
+        x = Dense(k, nout, out)
+        return (x, inf) if info else x
+
+    def inv_block(self, rows, cols) -> np.ndarray:
+        """``A^-1[rows, cols]`` for ANY rows and columns (A's order), an array
+        of shape ``len(rows) x len(cols)`` of the factor's dtype: the
+        :meth:`solve_sparse` of the unit columns ``e_cols`` at ``rows``, so
+        entry ``(i, j)`` has the bits of ``solve``'s row ``rows[i]`` for the
+        right-hand side ``e_cols[j]``. Where :meth:`inv_entries` refuses a
+        pair off the pattern of ``L + L^T``, this answers. ``rows`` / ``cols``
+        as ``solve_sparse``'s ``rows``."""
+        self._h()
+        r = self._rows_arg("inv_block", "rows", rows)
+        c = self._rows_arg("inv_block", "cols", cols)
+        k = c.shape[0]
+        col_ptr = np.arange(k + 1, dtype=np.uint64)
+        out, _ = self._solve_sparse(k, col_ptr, c, np.ones(k, dtype=self.dtype), r)
+        return np.stack(out, axis=1) if k else np.zeros((r.shape[0], 0), dtype=self.dtype)
+
     def logdet(self) -> float:
         """``log det A = 2 sum log L_ii`` (``bsm_nd_factor_logdet``), summed in
         f64 in a fixed order: the same bits on every call."""

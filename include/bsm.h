@@ -526,6 +526,41 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    the refined and pcg solves and eigsh all see the new factor. The factor's
  *    dtype, explicit fma, no atomics, a fixed order: the same call on the same
  *    factor gives the same bits. Synchronous.
+ *  - bsm_nd_factor_solve_sparse: A x = b (A's order) for a SPARSE b, with x
+ *    wanted at some rows only (CHOLMOD's Bset / Xset): a Green's function
+ *    between two points, an entry or a block of A^-1 off the pattern of
+ *    L + L^T. b is n x k, column-compressed on the host as
+ *    bsm_nd_factor_updown's W (col_ptr has k + 1 entries, rows strictly
+ *    ascending within a column); vals and x have the FACTOR's dtype, as
+ *    bsm_nd_factor_solve. xrows: nq rows, unsorted and repeated as the caller
+ *    likes, output row e is x[xrows[e]], and x_cols are k host columns of nq
+ *    values; xrows == NULL (with nq == 0): every row, x_cols are k columns of
+ *    n. Only the fronts on the paths from b's entries to the root run the
+ *    forward pass (every other front has y = 0), only those from the requested
+ *    rows' fronts to the root the backward pass; each of them performs the
+ *    dense solve's operations in its order, so every value returned EQUALS
+ *    bsm_nd_factor_solve's on the densified b (a zero may differ in sign: a
+ *    skipped front's +0 is not added to a -0). The values at a row depend
+ *    neither on the other rows asked for nor on the call's other columns, and
+ *    repeat bit for bit. With xrows == NULL the backward pass is the dense
+ *    solve's own. Columns go in chunks of 32: the temporaries never exceed the
+ *    dense solve's for 32 columns. An empty column gives a zero column and
+ *    activates nothing; stored zeros are ordinary entries; k == 0 is a no-op
+ *    (nothing is written, info included); nq == 0 with a non-NULL xrows is
+ *    valid, writes no x and sets info to 0. info (uint32[4] or NULL): the
+ *    fronts the forward pass ran on (the union over the columns), the fronts
+ *    the backward pass ran on, the fronts in the plan, the column chunks.
+ *    Errors, in this order, all before any device write: a null f, a null
+ *    among x_cols (or one of its k columns) / col_ptr / rows / vals where it
+ *    is read, col_ptr not ascending from 0 or rows not strictly ascending
+ *    within a column, nq > 0 with xrows == NULL -> BSM_ERR_INVALID; a row of b
+ *    or of xrows >= n -> BSM_ERR_OUT_OF_BOUNDS; another device, a handle
+ *    without values (a failed refactor) -> BSM_ERR_INVALID as for the solves.
+ *    A refused call leaves x_cols and info as they were. Takes the handle's
+ *    mutex, as the solves do. Synchronous.
+ *  - bsm_dev_nd_factor_solve_sparse: the same with x in HBM on the factor's
+ *    device, ROW-major nq x k (n x k); b and xrows stay on the host. Runs on
+ *    `stream`, returns after it has drained.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -572,6 +607,12 @@ int bsm_dev_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const 
                                 void* vecs, double* resid, uint32_t* info, void* stream);
 int bsm_nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
                          const void* vals);
+int bsm_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                               const void* vals, uint64_t nq, const uint64_t* xrows, void* const* x_cols,
+                               uint32_t* info);
+int bsm_dev_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
+                                   const void* vals, uint64_t nq, const uint64_t* xrows, void* x, uint32_t* info,
+                                   void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

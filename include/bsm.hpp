@@ -895,6 +895,49 @@ public:
         requires std::is_floating_point_v<U>
     void downdate(const Csr<U>& w) { updown(w, -1, "NdFactor::downdate"); }
 
+    /// x = A^-1 b for a SPARSE b (n x k, of the factor's dtype), x wanted at
+    /// `rows` only (bsm_nd_factor_solve_sparse): result row e is x[rows[e]]
+    /// (A's order, unsorted and repeated as the caller likes); rows == nullptr:
+    /// every row. Only the fronts on the paths from b's entries and from the
+    /// requested rows' fronts to the root are visited, with the dense solve's
+    /// operations in its order: every value equals solve()'s on the densified
+    /// b (a zero may differ in sign). info: the C call's four counts, or null.
+    /// Another row count: Panic; a row >= n throws as the C call reports it.
+    Dense<T> solve_sparse(const Csr<T>& b, const std::vector<uint64_t>* rows = nullptr,
+                          std::array<uint32_t, 4>* info = nullptr) const {
+        if (b.get_dims().rows != n_) throw Panic("NdFactor::solve_sparse: IncorrectDimensions");
+        // column-compressed: a counting sort by column keeps the rows ascending within each
+        const size_t k = b.get_dims().cols, nnz = b.v().size();
+        std::vector<uint64_t> cp(k + 1, 0), br(nnz);
+        std::vector<T> vals(nnz);
+        for (size_t c : b.col_index()) ++cp[c + 1];
+        for (size_t c = 0; c < k; ++c) cp[c + 1] += cp[c];
+        std::vector<uint64_t> at(cp.begin(), cp.end() - 1);
+        const auto& rp = b.row_index();
+        for (size_t r = 0; r + 1 < rp.size(); ++r)
+            for (size_t e = rp[r]; e < rp[r + 1]; ++e) {
+                const uint64_t o = at[b.col_index()[e]]++;
+                br[o] = r;
+                vals[o] = b.v()[e];
+            }
+        return solve_sparse_cc(k, cp, br, vals, rows, info);
+    }
+
+    /// A^-1[rows, cols] for ANY rows and columns (A's order), row-major
+    /// rows.size() x cols.size(): solve_sparse of the unit columns e_cols at
+    /// `rows`. Where inv_entries refuses a pair off the pattern of L + L^T,
+    /// this answers.
+    std::vector<T> inv_block(const std::vector<uint64_t>& rows, const std::vector<uint64_t>& cols) const {
+        const size_t k = cols.size(), nq = rows.size();
+        std::vector<uint64_t> cp(k + 1);
+        for (size_t c = 0; c <= k; ++c) cp[c] = c;
+        const Dense<T> x = solve_sparse_cc(k, cp, cols, std::vector<T>(k, T(1)), &rows, nullptr);
+        std::vector<T> out(nq * k);
+        for (size_t j = 0; j < k; ++j)
+            for (size_t i = 0; i < nq; ++i) out[i * k + j] = x.get_col(j)[i];
+        return out;
+    }
+
     /// log det A = 2 sum log L_ii, summed in f64 in a fixed order.
     double logdet() const {
         double v = 0.0;
@@ -1101,6 +1144,22 @@ public:
 
 private:
     NdFactor() = default;
+    // b column-compressed; an empty `rows` is passed as a non-null pointer (null means every row)
+    Dense<T> solve_sparse_cc(size_t k, const std::vector<uint64_t>& cp, const std::vector<uint64_t>& br,
+                             const std::vector<T>& vals, const std::vector<uint64_t>* rows,
+                             std::array<uint32_t, 4>* info) const {
+        const size_t nout = rows ? rows->size() : n_;
+        Dense<T> out = Dense<T>::new_default_with_dims(k, nout);
+        std::vector<void*> out_cols(k);
+        for (size_t j = 0; j < k; ++j) out_cols[j] = out.get_col_mut(j).data();
+        const uint64_t none = 0;
+        uint32_t inf[4] = {0, 0, 0, 0};
+        detail::check(bsm_nd_factor_solve_sparse(f_.get(), k, cp.data(), br.data(), vals.data(), rows ? rows->size() : 0,
+                                                 rows ? (rows->empty() ? &none : rows->data()) : nullptr,
+                                                 out_cols.data(), inf));
+        if (info) *info = {inf[0], inf[1], inf[2], inf[3]};
+        return out;
+    }
     template <class U>
     void updown(const Csr<U>& w, int sign, const char* what) {
         if (w.get_dims().rows != n_) throw Panic(std::string(what) + ": IncorrectDimensions");

@@ -172,6 +172,10 @@ def main():
     ap.add_argument("--updown", default=None, metavar="K[,K...]",
                     help="only the update / downdate record: K random stored edges as one call, then the same call "
                          "as a downdate, against refactor (profiles/nd_updown_c5.jsonl), for each K <= 16 given")
+    ap.add_argument("--sparse-rhs", action="store_true",
+                    help="only the sparse right-hand side record: one entry in and one row out, one entry in and "
+                         "every row out, 32 point sources with 32 rows, against the dense solve "
+                         "(profiles/nd_sparse_c5.jsonl)")
     ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
                     help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
                          "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
@@ -189,6 +193,14 @@ def main():
         with open(os.path.join(ROOT, "profiles", "nd_updown_c5.jsonl"), "a") as out:
             for line in nd_updown_ops(A, B, [int(k) for k in args.updown.split(",")], max(args.reps, 1),
                                       (n, rp, ci, v)):
+                print(json.dumps(line), flush=True)
+                out.write(json.dumps(line) + "\n")
+        return
+    if args.sparse_rhs:
+        _lib.stage_timing(True)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "nd_sparse_c5.jsonl"), "a") as out:
+            for line in nd_sparse_rhs_ops(A, B, max(args.reps, 1), (n, rp, ci, v)):
                 print(json.dumps(line), flush=True)
                 out.write(json.dumps(line) + "\n")
         return
@@ -632,6 +644,83 @@ def nd_updown_ops(A, B, ks, reps, pattern):
             line["python_update_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
             f.refactor(A)
             lines.append(line)
+    return lines
+
+
+def nd_sparse_rhs_ops(A, B, reps, pattern):
+    """The kept factor's solve with sparse right-hand sides and selected rows
+    (bsm_nd_factor_solve_sparse) against the dense solve, in the factor's dtype:
+    host wall ms around the synchronous C-ABI call on arrays built beforehand
+    (medians of `reps` after one warm-up), with the call's info (forward
+    fronts, backward fronts, fronts in the plan, column chunks) and its stages
+    by mark. Cases: one entry in and one row out (two seeded vertices); one
+    entry in and every row out; 32 point sources and 32 rows. Each is checked
+    for equality with the dense solve at the rows asked for. dense: the same
+    clock around bsm_nd_factor_solve_system for one column and for 32, with
+    its forward / backward device ms. One JSON line per case, also appended to
+    profiles/nd_sparse_c5.jsonl."""
+    from basic_sparse_matrix_amd import cholesky_nd
+
+    n = pattern[0]
+    dt = A.dtype
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    lib = _lib.require_device()
+    rng = np.random.default_rng(4242)
+    src = rng.choice(n, size=32, replace=False).astype(np.uint64)
+    want_rows = rng.choice(n, size=32, replace=False).astype(np.uint64)
+    lines = []
+    with cholesky_nd(A) as f:
+        dense = {}
+        for k in (1, 32):
+            bd = [np.zeros(n, dtype=dt) for _ in range(k)]
+            for j in range(k):
+                bd[j][src[j]] = 1.0
+            xd = [np.zeros(n, dtype=dt) for _ in range(k)]
+            t, st = [], []
+            for _ in range(reps + 1):
+                t0 = time.perf_counter()
+                rc = lib.bsm_nd_factor_solve_system(f.handle, 0, k, n, _lib.ptr_array(bd), _lib.ptr_array(xd))
+                t.append(time.perf_counter() - t0)
+                assert rc == 0, _lib.last_error()
+                st.append(_lib.stage_times())
+            dense[k] = {"solve_only_ms": med(t[1:]),
+                        "stages_ms": {s: round(float(np.median([x.get(s, 0.0) for x in st[1:]])), 4)
+                                      for s in ("nd_forward", "nd_backward", "nd_copy_out")},
+                        "x": np.stack(xd, axis=1)}
+        cases = (("one entry in, one row out", 1, want_rows[:1]), ("one entry in, every row out", 1, None),
+                 ("32 point sources, 32 rows out", 32, want_rows))
+        for name, k, xr in cases:
+            cp = np.arange(k + 1, dtype=np.uint64)
+            br = np.ascontiguousarray(src[:k])
+            bv = np.ones(k, dtype=dt)
+            nout = n if xr is None else len(xr)
+            xs = [np.zeros(nout, dtype=dt) for _ in range(k)]
+            info = np.zeros(4, dtype=np.uint32)
+            t, st = [], []
+            for _ in range(reps + 1):
+                t0 = time.perf_counter()
+                rc = lib.bsm_nd_factor_solve_sparse(f.handle, k, _lib.ptr(cp), _lib.ptr(br), _lib.ptr(bv),
+                                                    0 if xr is None else nout, None if xr is None else _lib.ptr(xr),
+                                                    _lib.ptr_array(xs), _lib.ptr(info))
+                t.append(time.perf_counter() - t0)
+                assert rc == 0, _lib.last_error()
+                st.append(_lib.stage_times())
+            ref = dense[k]["x"] if xr is None else dense[k]["x"][xr.astype(np.int64)]
+            lines.append({
+                "metric": "C5 nd factor: sparse right-hand sides and selected rows against the dense solve "
+                          "(host wall ms around the C call, medians)",
+                "config": {"g": int(round(n ** 0.5)), "case": name, "k": k, "rows_out": int(nout), "calls": reps,
+                           "dtype": str(np.dtype(dt))},
+                "solve_sparse_ms": med(t[1:]),
+                "solve_sparse_ms_min_max": [round(1e3 * min(t[1:]), 3), round(1e3 * max(t[1:]), 3)],
+                "info": {"forward_fronts": int(info[0]), "backward_fronts": int(info[1]), "fronts": int(info[2]),
+                         "chunks": int(info[3])},
+                "stages_ms": {s: round(float(np.median([x.get(s, 0.0) for x in st[1:]])), 4)
+                              for s in ("nd_sparse_owners", "nd_sparse_forward", "nd_sparse_backward",
+                                        "nd_sparse_gather")},
+                "equals_dense": bool(np.array_equal(np.stack(xs, axis=1), ref)),
+                "dense_solve_only_ms": dense[k]["solve_only_ms"],
+                "dense_stages_ms": dense[k]["stages_ms"]})
     return lines
 
 

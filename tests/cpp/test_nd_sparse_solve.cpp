@@ -1,0 +1,115 @@
+// bsm::NdFactor<T>::solve_sparse / inv_block (include/bsm.hpp) on a 2-D
+// Poisson system: a sparse b of three columns (two point sources and an empty
+// column) at a few rows and at every row equals the dense solve of the
+// densified b, entry for entry; inv_block equals the solves of unit columns;
+// the counts say that fronts were skipped; a b of another row count and a row
+// >= n are refused.
+//   (no argument)        the GPU run
+//   --expect-no-device   the constructor must throw bsm::DeviceError
+#include <array>
+#include <cstdio>
+#include <cstring>
+#include <stdexcept>
+#include <vector>
+
+#include "bsm.hpp"
+#include "../../oracle/bsm_oracle.h"
+
+using bsm::Csr;
+using bsm::Dense;
+
+static int g_fail = 0, g_checks = 0;
+#define CHECK(cond)                                                        \
+    do {                                                                   \
+        ++g_checks;                                                        \
+        if (!(cond)) {                                                     \
+            ++g_fail;                                                      \
+            std::fprintf(stderr, "  CHECK failed: %s (line %d)\n", #cond, __LINE__); \
+        }                                                                  \
+    } while (0)
+
+static Csr<double> poisson(uint64_t g) {
+    const uint64_t n = g * g;
+    std::vector<uint64_t> rp(n + 1), ci(5 * n);
+    std::vector<double> v(5 * n);
+    const uint64_t nnz = orc_gen_poisson2d(g, rp.data(), ci.data(), v.data());
+    ci.resize(nnz);
+    v.resize(nnz);
+    return Csr<double>::from_csr_arrays({n, n}, {rp.begin(), rp.end()}, {ci.begin(), ci.end()}, v);
+}
+
+template <class F>
+static bool throws(F&& f) {
+    try {
+        f();
+    } catch (const std::exception&) {
+        return true;
+    }
+    return false;
+}
+
+static void run_gpu() {
+    const uint64_t g = 11, n = g * g;
+    bsm::NdFactor<double> f(poisson(g));
+    std::vector<std::vector<double>> bd(n, std::vector<double>(3, 0.0));  // rows of b
+    bd[5][0] = 1.0;
+    bd[97][0] = -0.5;
+    bd[60][2] = 2.0;
+    const auto b = Csr<double>::from_data(bd);
+    std::vector<std::vector<double>> cols(3, std::vector<double>(n, 0.0));
+    for (uint64_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c) cols[c][i] = bd[i][c];
+    const auto want = f.solve(Dense<double>::from_data(cols));
+    const std::vector<uint64_t> rows = {120, 0, 60, 60, 5};
+    std::array<uint32_t, 4> info{};
+    const auto x = f.solve_sparse(b, &rows, &info);
+    CHECK(x.get_dims().rows == rows.size() && x.get_dims().cols == 3);
+    for (size_t c = 0; c < 3; ++c)
+        for (size_t e = 0; e < rows.size(); ++e) CHECK(x.get_col(c)[e] == want.get_col(c)[rows[e]]);
+    CHECK(info[0] > 0 && info[0] < info[2] && info[1] > 0 && info[1] < info[2] && info[3] == 1);
+    const auto xa = f.solve_sparse(b);
+    CHECK(xa.get_dims().rows == n);
+    for (size_t c = 0; c < 3; ++c)
+        for (uint64_t i = 0; i < n; ++i) CHECK(xa.get_col(c)[i] == want.get_col(c)[i]);
+    const std::vector<uint64_t> none;
+    CHECK(f.solve_sparse(b, &none).get_dims().rows == 0);
+    // inv_block against the solves of unit columns
+    const std::vector<uint64_t> bc = {5, 60};
+    std::vector<std::vector<double>> unit(2, std::vector<double>(n, 0.0));
+    unit[0][5] = 1.0;
+    unit[1][60] = 1.0;
+    const auto z = f.solve(Dense<double>::from_data(unit));
+    const auto blk = f.inv_block(rows, bc);
+    CHECK(blk.size() == rows.size() * 2);
+    for (size_t e = 0; e < rows.size(); ++e)
+        for (size_t j = 0; j < 2; ++j) CHECK(blk[e * 2 + j] == z.get_col(j)[rows[e]]);
+    // refusals
+    bd.push_back({0.0, 0.0, 1.0});
+    CHECK(throws([&] { f.solve_sparse(Csr<double>::from_data(bd)); }));
+    const std::vector<uint64_t> far = {n};
+    CHECK(throws([&] { f.solve_sparse(b, &far); }));
+    CHECK(throws([&] { f.inv_block(rows, far); }));
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "--expect-no-device") == 0) {
+        bool dev_err = false;
+        try {
+            bsm::NdFactor<double> f(poisson(4));
+            f.solve_sparse(Csr<double>::from_data({{1.0}}));
+        } catch (const bsm::DeviceError&) {
+            dev_err = true;
+        } catch (...) {
+        }
+        std::printf("%s NdFactor (DeviceError without a GPU: no CPU fallback)\n", dev_err ? "PASS" : "FAIL");
+        return dev_err ? 0 : 1;
+    }
+    try {
+        run_gpu();
+    } catch (const std::exception& e) {
+        ++g_fail;
+        std::fprintf(stderr, "  EXCEPTION: %s\n", e.what());
+    }
+    std::printf("summary: %d failed, %d checks\n", g_fail, g_checks);
+    return g_fail ? 1 : 0;
+}
