@@ -10,7 +10,17 @@ hand-written HIP kernels through the C-ABI in include/bsm.h
 from .dense import Dense
 from .dense_static import DenseS
 from .multi import set_gpus
-from .solver import EigInfo, NdFactor, PcgInfo, RefineInfo, backward_substitution, cholesky_nd, forward_substitution, solve
+from .solver import (
+    EigInfo,
+    NdFactor,
+    PartialInfo,
+    PcgInfo,
+    RefineInfo,
+    backward_substitution,
+    cholesky_nd,
+    forward_substitution,
+    solve,
+)
 from .sparse import COO, COOEntry, Csr, CsrEntry
 from .util import GetDims, MatDim, MatErr, MatErrKind, Panic
 
@@ -33,6 +43,7 @@ __all__ = [
     "cholesky_nd",
     "NdFactor",
     "EigInfo",
+    "PartialInfo",
     "PcgInfo",
     "RefineInfo",
 ]

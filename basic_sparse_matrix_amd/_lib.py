@@ -132,6 +132,8 @@ SIGNATURES = [
     ("bsm_nd_factor_updown", _int, [_vp, _int, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_solve_sparse", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _pp, _vp]),
     ("bsm_dev_nd_factor_solve_sparse", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("bsm_nd_factor_refactor_partial", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    ("bsm_nd_factor_refactor_since", _int, [_vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),

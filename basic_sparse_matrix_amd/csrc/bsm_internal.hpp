@@ -283,6 +283,9 @@ struct bsm_nd_factor {
     std::shared_ptr<bsm::DBuf> pattern;
     uint64_t nnz = 0;   // that pattern's entries
     bool valid = true;  // false after a refactorisation that failed past its checks: fr / dv hold no factor (under mu)
+    // an update / downdate has rewritten pivot panels since the last numeric factorisation: the children's update
+    // blocks left in the trailing tiles no longer belong to them, so a partial refactor must not pull them (under mu)
+    bool stale_blocks = false;
 };
 
 namespace bsm {
@@ -426,6 +429,15 @@ int nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, uint64_t nnz_w, con
 int nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
                            const void* vals, uint64_t nq, const uint64_t* xrows, void* x_dev, uint32_t* info,
                            hipStream_t s);
+// New values at a few named places of the factored pattern:
+// the fronts on the paths from those entries to the roots are factored again,
+// with the bits of nd_factor_refactor(f, a). rows / cols: nc pairs on the HOST,
+// any order, (j, i) as good as (i, j), repeats allowed. a_old != null (the
+// `since` form, rows / cols ignored): the places are the stored entries with
+// col <= row whose bits differ between a_old and a. info: 3 entries or null
+// (active fronts, fronts in the plan, changed entries). Synchronous on s.
+int nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a, uint64_t nc,
+                               const uint64_t* rows, const uint64_t* cols, uint64_t* info, hipStream_t s);
 // mixed precision on a kept factor (kernels_refine.hip)
 // n float values into the other float dtype, round-to-nearest (async on s)
 int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s);

@@ -1327,6 +1327,23 @@ int bsm_nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a) {
     return nd_factor_refactor(f, a, s);
 }
 
+int bsm_nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a, uint64_t nc, const uint64_t* rows,
+                                   const uint64_t* cols, uint64_t* info) {
+    BSM_REQUIRE(f && a, BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(nc == 0 || (rows && cols), BSM_ERR_INVALID,
+                "nd factor refactor_partial: nc = %llu pairs named but rows or cols is null", (unsigned long long)nc);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_refactor_partial(f, nullptr, a, nc, rows, cols, info, s);
+}
+
+int bsm_nd_factor_refactor_since(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a_new, uint64_t* info) {
+    BSM_REQUIRE(f && a_old && a_new, BSM_ERR_INVALID, "null argument");
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    return nd_factor_refactor_partial(f, a_old, a_new, 0, nullptr, nullptr, info, s);
+}
+
 int bsm_nd_factor_logdet(const bsm_nd_factor* f, double* logdet) {
     BSM_REQUIRE(f && logdet, BSM_ERR_INVALID, "null argument");
     hipStream_t s;

@@ -109,6 +109,17 @@ class RefineInfo:
 
 
 @dataclass
+class PartialInfo:
+    """What ``NdFactor.refactor_partial`` reports: the fronts factored again,
+    the fronts in the plan, and the changed entries (as named, or as found
+    with ``since=``)."""
+
+    fronts: int
+    total_fronts: int
+    changed: int
+
+
+@dataclass
 class PcgInfo:
     """What a pcg solve reports per right-hand column: the CG steps made, the
     backward error of the returned ``x`` (of its true residual), whether it
@@ -249,7 +260,8 @@ class NdFactor:
     device (``bsm_nd_factor``): factor once with :func:`cholesky_nd`, then
     ``solve`` as often as wanted (``A``, ``L`` or ``L^T``), read ``L`` or
     ``logdet()`` out, and ``refactor`` new values of the same pattern in
-    place (``device.nd_factor_solve`` solves on device tensors), and read the
+    place (``refactor_partial`` where only a few entries changed;
+    ``device.nd_factor_solve`` solves on device tensors), and read the
     selected inverse (``inv_diag()``, ``inv_entries()``, ``inv_on()``:
     ``A^-1`` on the pattern of ``L + L^T``). ``solve_refined`` refines a
     solve with f64 residuals and reports its backward error, ``solve_pcg``
@@ -461,6 +473,58 @@ class NdFactor:
         h = self._h()
         dev = a._device()
         _raise_for(_lib.require_device().bsm_nd_factor_refactor(h, dev.handle))
+
+    def refactor_partial(self, a: Csr, rows=None, cols=None, *, since: Csr | None = None) -> PartialInfo:
+        """New values at a FEW places of the factored pattern
+        (``bsm_nd_factor_refactor_partial``): only the fronts on the paths
+        from the changed entries to the roots of the separator tree are
+        factored again, and the factor has the bits ``refactor(a)`` gives.
+        Give exactly one of
+
+        * ``rows, cols``: the changed positions as two equally long 1-D
+          integer sequences, any order, ``(j, i)`` as good as ``(i, j)``,
+          repeats allowed; every pair must be a stored entry of ``a``;
+        * ``since=a_old``: the matrix this is the factor of; the stored
+          entries with ``col <= row`` whose bits differ are found on the
+          device (``bsm_nd_factor_refactor_since``).
+
+        ``a`` equals the factored matrix in every other stored entry with
+        ``col <= row``; a changed entry that is not named gives an
+        unspecified factor. After ``update`` / ``downdate`` the call raises
+        the error for ``BSM_ERR_UNSUPPORTED`` until a ``refactor``. Pattern,
+        shape and dtype are checked as ``refactor`` checks them; a pair that
+        is not stored raises the error for ``BSM_ERR_INVALID``, an index
+        ``>= n`` ``MatErr(OutOfBounds)``, all with the factor untouched.
+        Values that are not positive definite leave the handle without a
+        factor, as a failed ``refactor`` does. Returns
+        :class:`PartialInfo`."""
+        what = "NdFactor.refactor_partial"
+        named = rows is not None or cols is not None
+        if named == (since is not None):
+            raise ValueError(f"{what}: give exactly one of (rows, cols) and since=")
+        _check_factorable(a, what)
+        h = self._h()
+        info = np.zeros(3, dtype=np.uint64)
+        lib = _lib.require_device
+        if since is not None:
+            if not isinstance(since, Csr):
+                raise TypeError(f"{what}: since must be a Csr, got {type(since).__name__}")
+            _check_factorable(since, what)
+            if since.dtype != a.dtype:
+                raise TypeError(f"{what}: since is Csr<{since.dtype}>, a is Csr<{a.dtype}>")
+            _raise_for(lib().bsm_nd_factor_refactor_since(h, since._device().handle, a._device().handle,
+                                                          _lib.ptr(info)))
+        else:
+            if rows is None or cols is None:
+                raise ValueError(f"{what}: rows and cols go together")
+            r = self._rows_arg("refactor_partial", "rows", rows)
+            c = self._rows_arg("refactor_partial", "cols", cols)
+            if r.shape[0] != c.shape[0]:
+                raise ValueError(f"{what}: rows has {r.shape[0]} entries, cols {c.shape[0]}")
+            nc = r.shape[0]
+            _raise_for(lib().bsm_nd_factor_refactor_partial(h, a._device().handle, nc, _lib.ptr(r) if nc else None,
+                                                            _lib.ptr(c) if nc else None, _lib.ptr(info)))
+        return PartialInfo(int(info[0]), int(info[1]), int(info[2]))
 
     def _updown(self, w: Csr, sign: int, what: str) -> None:
         h = self._h()

@@ -561,6 +561,45 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *  - bsm_dev_nd_factor_solve_sparse: the same with x in HBM on the factor's
  *    device, ROW-major nq x k (n x k); b and xrows stay on the host. Runs on
  *    `stream`, returns after it has drained.
+ *  - bsm_nd_factor_refactor_partial: new values at a FEW places of the
+ *    factored pattern (a Newton or contact step in which a few elements
+ *    change, a device that switches, a local material change): only the fronts
+ *    on the paths from those entries to the roots of the separator tree are
+ *    factored again, by refactor's own kernel on refactor's per-tile inputs in
+ *    refactor's order. Precondition: f holds the factor of some a0 on its
+ *    pattern, made by bsm_nd_factor_create(_as), bsm_nd_factor_refactor or an
+ *    earlier partial call, and no bsm_nd_factor_updown has run since. a has
+ *    that pattern (checked as bsm_nd_factor_refactor checks it, with its
+ *    errors and messages) and equals a0 in every stored entry (i, j), j <= i,
+ *    except possibly at the nc positions (rows[e], cols[e]): host arrays, any
+ *    order, (j, i) names the same entry as (i, j), repeats allowed. Entries
+ *    above the diagonal are not read, as ever. Afterwards f is the factor of a
+ *    and every bit of it that anything reads equals what
+ *    bsm_nd_factor_refactor(f, a) writes. A changed entry that is NOT named
+ *    gives an unspecified factor (bsm_nd_factor_refactor_since finds the
+ *    places itself). info (uint64[3] or NULL): the fronts factored again, the
+ *    fronts in the plan, the changed entries (nc as named). Errors, all before
+ *    any write to the factor: a null f or a, then nc > 0 with a null rows or
+ *    cols -> BSM_ERR_INVALID (no device asked for); another device, dtype,
+ *    shape, nnz, row_ptr or col -> bsm_nd_factor_refactor's; an index >= n ->
+ *    BSM_ERR_OUT_OF_BOUNDS; a handle on which an update or downdate has run
+ *    since its last factorisation -> BSM_ERR_UNSUPPORTED (refactor first: the
+ *    update blocks the active fronts would pull are stale); a named pair that
+ *    is not a stored entry of a -> BSM_ERR_INVALID with their number and the
+ *    first one. nc == 0 runs the checks and leaves the factor's bits (info:
+ *    0 fronts); n == 0 is a no-op. A pivot <= 0 or not finite met while
+ *    writing leaves the handle without values exactly as a failed
+ *    bsm_nd_factor_refactor does (BSM_ERR_UNSUPPORTED, its message; a later
+ *    bsm_nd_factor_refactor restores it); a handle already without values is
+ *    given the full factorisation of a (every front reported), and so is one
+ *    on the plain pipeline (BSM_ND_PLAIN=1, or 2^31 stored entries or more),
+ *    which assembles into the fronts and cannot restart one. nnz_l reads 0
+ *    until the next export. Takes the handle's mutex. Synchronous.
+ *  - bsm_nd_factor_refactor_since: the same for callers who cannot name the
+ *    places: a_old (the matrix f is the factor of) and a_new, both on f's
+ *    pattern, are compared on the device, and every stored entry with
+ *    col <= row whose bits differ (so NaN and -0 count) is a changed place.
+ *    info[2] is their number. No differing entry: the factor's bits stay.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -613,6 +652,9 @@ int bsm_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_
 int bsm_dev_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
                                    const void* vals, uint64_t nq, const uint64_t* xrows, void* x, uint32_t* info,
                                    void* stream);
+int bsm_nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a, uint64_t nc, const uint64_t* rows,
+                                   const uint64_t* cols, uint64_t* info);
+int bsm_nd_factor_refactor_since(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a_new, uint64_t* info);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).

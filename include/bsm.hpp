@@ -874,6 +874,45 @@ public:
         detail::check(bsm_nd_factor_refactor(f_.get(), h.get()));
     }
 
+    /// New values at the named places (rows[e], cols[e]) of the factored
+    /// pattern alone (bsm_nd_factor_refactor_partial): only the fronts on the
+    /// paths from those entries to the roots are factored again, and the
+    /// factor has the bits refactor(a) gives. a equals the factored matrix in
+    /// every other stored entry with col <= row; no update / downdate has run
+    /// since the last factorisation (else DeviceError: refactor first). A pair
+    /// that is not stored, an index >= n, another pattern or dtype throw and
+    /// leave the factor untouched. Returns {fronts factored again, fronts in
+    /// the plan, changed entries}.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    std::array<uint64_t, 3> refactor_partial(const Csr<U>& a, const std::vector<uint64_t>& rows,
+                                             const std::vector<uint64_t>& cols) {
+        if (a.get_dims().rows != a.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        if (rows.size() != cols.size())
+            throw std::invalid_argument("NdFactor::refactor_partial: rows and cols differ in length");
+        auto h = a.device();
+        std::array<uint64_t, 3> info{0, 0, 0};
+        detail::check(bsm_nd_factor_refactor_partial(f_.get(), h.get(), rows.size(), rows.data(), cols.data(),
+                                                     info.data()));
+        return info;
+    }
+
+    /// The same with the places found on the device (bsm_nd_factor_refactor_since):
+    /// the stored entries with col <= row whose bits differ between a_old (the
+    /// matrix this is the factor of) and a_new.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    std::array<uint64_t, 3> refactor_since(const Csr<U>& a_old, const Csr<U>& a_new) {
+        if (a_new.get_dims().rows != a_new.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        auto ho = a_old.device();
+        auto hn = a_new.device();
+        std::array<uint64_t, 3> info{0, 0, 0};
+        detail::check(bsm_nd_factor_refactor_since(f_.get(), ho.get(), hn.get(), info.data()));
+        return info;
+    }
+
     /// The factor of P (S + W W^T) P^T in place (bsm_nd_factor_updown), S the
     /// matrix this was the factor of, w of shape n x k, 1 <= k <= 16, of the
     /// FACTORED MATRIX's dtype (another one throws std::invalid_argument,

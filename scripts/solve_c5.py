@@ -176,6 +176,10 @@ def main():
                     help="only the sparse right-hand side record: one entry in and one row out, one entry in and "
                          "every row out, 32 point sources with 32 rows, against the dense solve "
                          "(profiles/nd_sparse_c5.jsonl)")
+    ap.add_argument("--partial", default=None, metavar="K[,K...]",
+                    help="only the partial refactor record: K seeded stored entries changed and named as one call, "
+                         "against refactor in the same session, and one line with an f32 factor "
+                         "(profiles/nd_partial_c5.jsonl)")
     ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
                     help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
                          "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
@@ -201,6 +205,15 @@ def main():
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "nd_sparse_c5.jsonl"), "a") as out:
             for line in nd_sparse_rhs_ops(A, B, max(args.reps, 1), (n, rp, ci, v)):
+                print(json.dumps(line), flush=True)
+                out.write(json.dumps(line) + "\n")
+        return
+    if args.partial:
+        _lib.stage_timing(True)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "nd_partial_c5.jsonl"), "a") as out:
+            for line in nd_partial_ops(A, B, [int(k) for k in args.partial.split(",")], max(args.reps, 1),
+                                       (n, rp, ci, v)):
                 print(json.dumps(line), flush=True)
                 out.write(json.dumps(line) + "\n")
         return
@@ -721,6 +734,94 @@ def nd_sparse_rhs_ops(A, B, reps, pattern):
                 "equals_dense": bool(np.array_equal(np.stack(xs, axis=1), ref)),
                 "dense_solve_only_ms": dense[k]["solve_only_ms"],
                 "dense_stages_ms": dense[k]["stages_ms"]})
+    return lines
+
+
+def nd_partial_ops(A, B, ks, reps, pattern):
+    """The kept factor's partial refactor (bsm_nd_factor_refactor_partial)
+    against refactor in the same session: K seeded stored entries with
+    col <= row get new values (a diagonal entry + 1/4, an edge 3/4 of its value:
+    the matrix stays diagonally dominant) and are named in one call; the next
+    call names them again with the first matrix's values, so every call is a
+    partial refactor of K changed entries. Host wall ms around the synchronous
+    C-ABI call on device handles made beforehand (medians of `reps` after one
+    warm-up pair), the call's info and its stages by mark (owners: the checks
+    and the start fronts; select: the task selection and the values; factor:
+    nd_factor on the active fronts). refactor: the same clock around
+    bsm_nd_factor_refactor, before and after the partial calls. equals_fresh:
+    solve(b) and logdet() against cholesky_nd of the changed matrix, by bits.
+    One JSON line per K in the matrix's dtype, then one with an f32 factor for
+    the first K; also appended to profiles/nd_partial_c5.jsonl."""
+    from basic_sparse_matrix_amd import cholesky_nd
+
+    n, rp, ci, v = pattern
+    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
+    cols = ci.astype(np.int64)
+    lower = np.flatnonzero(cols <= rows)
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    lib = _lib.require_device()
+    ha = A._device().handle
+    lines = []
+
+    def refactor_ms(f):
+        t = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            rc = lib.bsm_nd_factor_refactor(f.handle, ha)
+            t.append(time.perf_counter() - t0)
+            assert rc == 0, _lib.last_error()
+        return t[1:], {k: round(x, 4) for k, x in _lib.stage_times().items()}
+
+    for fdt in (A.dtype, np.dtype(np.float32)):
+        if fdt != A.dtype:
+            ks = ks[:1]
+        Bf = Dense.from_columns([np.ascontiguousarray(np.asarray(B.get_col(0)).astype(fdt))])
+        with cholesky_nd(A, factor_dtype=fdt) as f:
+            t_ref, ref_stages = refactor_ms(f)
+            for K in ks:
+                pick = np.random.default_rng(2000 + K).choice(lower, size=K, replace=False)
+                v2 = np.array(v)
+                v2[pick] = np.where(rows[pick] == cols[pick], v[pick] + 0.25, 0.75 * v[pick])
+                A2 = Csr.from_csr_arrays((n, n), rp, ci, v2)
+                h2 = A2._device().handle
+                r = np.ascontiguousarray(rows[pick].astype(np.uint64))
+                c = np.ascontiguousarray(cols[pick].astype(np.uint64))
+                info = np.zeros(3, dtype=np.uint64)
+                times, stages = {"new": [], "old": []}, {"new": [], "old": []}
+                for _ in range(reps + 1):  # the first pair warms the temporaries
+                    for key, h in (("new", h2), ("old", ha)):
+                        t0 = time.perf_counter()
+                        rc = lib.bsm_nd_factor_refactor_partial(f.handle, h, K, _lib.ptr(r), _lib.ptr(c), _lib.ptr(info))
+                        times[key].append(time.perf_counter() - t0)
+                        assert rc == 0, _lib.last_error()
+                        stages[key].append(_lib.stage_times())
+                rc = lib.bsm_nd_factor_refactor_partial(f.handle, h2, K, _lib.ptr(r), _lib.ptr(c), _lib.ptr(info))
+                assert rc == 0, _lib.last_error()
+                with cholesky_nd(A2, factor_dtype=fdt) as fresh:
+                    same = (np.array_equal(np.asarray(f.solve(Bf).get_col(0)), np.asarray(fresh.solve(Bf).get_col(0)))
+                            and f.logdet() == fresh.logdet())
+                rc = lib.bsm_nd_factor_refactor_partial(f.handle, ha, K, _lib.ptr(r), _lib.ptr(c), _lib.ptr(info))
+                assert rc == 0, _lib.last_error()
+                t_all = times["new"][1:] + times["old"][1:]
+                st_all = stages["new"][1:] + stages["old"][1:]
+                lines.append({
+                    "metric": "C5 nd factor: partial refactor of K changed stored entries against refactor "
+                              "(host wall ms around the C call, medians)",
+                    "config": {"g": int(round(n ** 0.5)), "K": int(K), "calls": len(t_all),
+                               "dtype": str(np.dtype(A.dtype)), "factor_dtype": str(np.dtype(fdt))},
+                    "active_fronts": int(info[0]), "fronts": int(info[1]), "changed": int(info[2]),
+                    "partial_ms": med(t_all),
+                    "partial_ms_min_max": [round(1e3 * min(t_all), 3), round(1e3 * max(t_all), 3)],
+                    "partial_stages_ms": {k: round(float(np.median([x.get(k, 0.0) for x in st_all])), 4)
+                                          for k in ("nd_partial_owners", "nd_partial_select", "nd_partial_factor")},
+                    "equals_fresh": bool(same),
+                    "refactor_ms": med(t_ref),
+                    "refactor_ms_min_max": [round(1e3 * min(t_ref), 3), round(1e3 * max(t_ref), 3)],
+                    "refactor_stages_ms": ref_stages})
+            t_after, _ = refactor_ms(f)
+            for line in lines:
+                if line["config"]["factor_dtype"] == str(np.dtype(fdt)):
+                    line["refactor_after_ms"] = med(t_after)
     return lines
 
 
