@@ -146,6 +146,8 @@ SIGNATURES = [
     ("bsm_dev_scan_workspace_bytes", _u64, [_u64]),
     ("bsm_dev_spmm", _int, [_int, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_csr_panel_cols", _int, [_vp, _u64p]),
+    ("bsm_dev_spmm_kernel", _int, [_int, _u64, _u64, _u64, _u64, _vp, _vp]),
+    ("bsm_dev_spmm_wants_split", _int, [_int, _u64, _u64]),
     ("bsm_dev_spmm_panel_cols", _u64, [_int, _u64, _u64]),
     ("bsm_dev_spmm_plan_bytes", _u64, [_u64, _u64, _u64]),
     ("bsm_dev_spmm_plan", _int, [_u64, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_int), _vp]),

@@ -331,6 +331,11 @@ int spmm_dispatch(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const
                   const int32_t* col, const void* vals, uint64_t k, const void* x, void* y,
                   int32_t* row_nnz, bool neg_zero_init, hipStream_t s,
                   uint64_t max_row_len = UINT64_MAX);  // the longest row, when known (kernel choice)
+// the kernel spmm_dispatch launches for these arguments under the environment
+// as it is now (spmm_rule.hpp; launch_spmm switches on this very call)
+enum class SpmmKernel : int;
+SpmmKernel spmm_kernel_choice(int dtype, uint64_t rows, uint64_t nnz, uint64_t k, uint64_t max_row_len,
+                              const void* x, const void* y);
 // nnz-balanced integer SpMM for skewed rows (zeroes y; row_nnz may be null)
 bool spmm_wants_split(int dtype, uint64_t k, uint64_t max_row_len);
 int spmm_split_dispatch(int dtype, uint64_t rows, uint64_t nnz, const int64_t* rp, const int32_t* col,

@@ -1617,6 +1617,23 @@ int bsm_dev_spmm(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const 
                          static_cast<hipStream_t>(stream));
 }
 
+int bsm_dev_spmm_kernel(int dtype, uint64_t rows, uint64_t nnz, uint64_t k, uint64_t max_row_len, const void* x,
+                        const void* y) {
+    if (dtype < BSM_F64 || dtype > BSM_U64) {
+        set_error("unknown dtype %d", dtype);
+        return -1;
+    }
+    return (int)spmm_kernel_choice(dtype, rows, nnz, k, max_row_len, x, y);
+}
+
+int bsm_dev_spmm_wants_split(int dtype, uint64_t k, uint64_t max_row_len) {
+    if (dtype < BSM_F64 || dtype > BSM_U64) {
+        set_error("unknown dtype %d", dtype);
+        return -1;
+    }
+    return spmm_wants_split(dtype, k, max_row_len) ? 1 : 0;
+}
+
 int bsm_csr_panel_cols(const bsm_csr* m, uint64_t* panel_cols) {
     BSM_REQUIRE(m && panel_cols, BSM_ERR_INVALID, "null argument");
     *panel_cols = m->plan_usable ? m->plan_cols : 0;

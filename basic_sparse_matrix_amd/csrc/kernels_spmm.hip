@@ -10,6 +10,7 @@
 // reference, not merely within tolerance. See DESIGN.md "SpMM kernels".
 #include "bsm_internal.hpp"
 #include "bsm_synth.h"
+#include "spmm_rule.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -944,111 +945,113 @@ namespace {
 // Kernel-variant override for A/B timing (BSM_SPMM_VARIANT): 0 default,
 // 1 generic row-wave, 2 k32 unpipelined, 3 k32 pipelined x4, 4 k32 pipelined x8,
 // 5 k32 four rows per wave (U = 4), 6 the same with U = 2.
-// entries per thread of spmv_stream (BSM_SPMV_ITEMS = 2, 4 or 8 for A/B)
-int spmv_items() {
+// entries per thread of spmv_stream (BSM_SPMV_ITEMS = 2, 4 or 8 for A/B);
+// BSM_SPMV_VARIANT: see spmm_rule.hpp, which turns the three into a kernel
+int spmv_items_env() {
     const char* e = getenv("BSM_SPMV_ITEMS");
-    const int v = e ? atoi(e) : 4;
-    return (v == 2 || v == 8) ? v : 4;
+    return e ? atoi(e) : 4;
 }
-constexpr uint64_t SHORT_ROW_AVG = 24;  // nnz/rows at or below: four rows per wave
-constexpr uint64_t SPMV_THREAD_ROWS = 16384, SPMV_THREAD_MAX_LEN = 48;  // spmv_thread's shapes
-constexpr uint64_t SPMV_ROWS_AVG = 12;  // k = 1, nnz/rows at or below: spmv_rows (one chunk per workgroup)
+int spmv_variant_env() {
+    const char* e = getenv("BSM_SPMV_VARIANT");
+    return e ? atoi(e) : 0;
+}
 int spmm_variant() {
     const char* e = getenv("BSM_SPMM_VARIANT");
     return e ? atoi(e) : 0;
 }
+}  // namespace
 
+// the kernel launch_spmm launches for this call, under the environment as it is now
+SpmmKernel spmm_kernel_choice(int dtype, uint64_t rows, uint64_t nnz, uint64_t k, uint64_t max_row_len,
+                              const void* x, const void* y) {
+    const bool aligned = ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0;
+    return spmm_kernel_rule(dtype == BSM_F64, dtype == BSM_F64 || dtype == BSM_F32, rows, nnz, k, max_row_len,
+                            aligned, spmv_variant_env(), spmv_items_env(), spmm_variant());
+}
+
+namespace {
 template <typename T>
-int launch_spmm(uint64_t rows, uint64_t nnz, const int64_t* rp, const int32_t* col,
+int launch_spmm(int dtype, uint64_t rows, uint64_t nnz, const int64_t* rp, const int32_t* col,
                 const T* vals, uint64_t k, const T* x, T* y, int32_t* row_nnz, bool neg_init,
                 hipStream_t s, uint64_t max_row_len) {
-    if (rows == 0) return BSM_OK;
-    // short rows on average (C2: 10): the rows-blocked SpMV; BSM_SPMV_VARIANT=1
-    // forces the nnz-balanced spmv_stream (A/B)
-    const char* sv = getenv("BSM_SPMV_VARIANT");
-    if (k == 1 && nnz <= SPMV_ROWS_AVG * rows && !(sv && atoi(sv) == 1)) {
-        const uint64_t blocks = (rows + 255) / 256;
-        BSM_REQUIRE(blocks < (1ull << 31), BSM_ERR_UNSUPPORTED, "too many rows for one launch");
-        const int64_t r = (int64_t)rows;
-        const int svv = sv ? atoi(sv) : 0;
-        if (svv == 2)  // the workgroup-chunk version (A/B)
-            spmv_rows<T, 16><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (svv == 3)
-            spmv_wave<T, 16><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (svv == 4)
-            spmv_wave<T, 12><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (svv == 5)
-            spmv_wave<T, 8><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (svv == 6)
-            spmv_thread<T, 12><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (svv == 0 && rows <= SPMV_THREAD_ROWS && max_row_len <= SPMV_THREAD_MAX_LEN)
-            // few short rows (C1: 1,024 x ~10): latency-bound, one thread per
-            // row has the fewest dependent round trips (4.5 against 6.4 us at
-            // C1, profiles/r05_z_*)
-            spmv_thread<T, 12><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        else  // default (C2: 111 us against 117-167 for the others, scripts/perf/spmv_variants.py)
-            spmv_wave<T, 8><<<(unsigned)blocks, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init);
-        BSM_HIP_TRY(hipGetLastError());
-        return BSM_OK;
-    }
+    const SpmmKernel kernel = spmm_kernel_choice(dtype, rows, nnz, k, max_row_len, x, y);
+    if (kernel == SpmmKernel::None) return BSM_OK;
+    const int64_t r = (int64_t)rows;
     if (k == 1) {
-        const int items = spmv_items();
-        const uint64_t blocks = nnz / (256ull * items) + 1;
-        BSM_REQUIRE(blocks < (1ull << 31), BSM_ERR_UNSUPPORTED, "nnz too large for one launch");
-        const int64_t r = (int64_t)rows, z = (int64_t)nnz;
-        if (items == 2)
-            spmv_stream<T, 2><<<(unsigned)blocks, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init);
-        else if (items == 8)
-            spmv_stream<T, 8><<<(unsigned)blocks, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init);
-        else
-            spmv_stream<T, 4><<<(unsigned)blocks, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init);
+        // the rows-blocked kernels: one row per thread; spmv_stream: CHUNK entries per workgroup
+        uint64_t blocks = (rows + 255) / 256;
+        const int items = kernel == SpmmKernel::SpmvStream2 ? 2 : kernel == SpmmKernel::SpmvStream8 ? 8 : 4;
+        const bool stream = kernel == SpmmKernel::SpmvStream2 || kernel == SpmmKernel::SpmvStream4 ||
+                            kernel == SpmmKernel::SpmvStream8;
+        if (stream) {
+            blocks = nnz / (256ull * items) + 1;
+            BSM_REQUIRE(blocks < (1ull << 31), BSM_ERR_UNSUPPORTED, "nnz too large for one launch");
+        } else {
+            BSM_REQUIRE(blocks < (1ull << 31), BSM_ERR_UNSUPPORTED, "too many rows for one launch");
+        }
+        const unsigned g = (unsigned)blocks;
+        const int64_t z = (int64_t)nnz;
+        switch (kernel) {
+        case SpmmKernel::SpmvRows16: spmv_rows<T, 16><<<g, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvWave16: spmv_wave<T, 16><<<g, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvWave12: spmv_wave<T, 12><<<g, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvWave8: spmv_wave<T, 8><<<g, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvThread12: spmv_thread<T, 12><<<g, 256, 0, s>>>(r, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvStream2: spmv_stream<T, 2><<<g, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvStream4: spmv_stream<T, 4><<<g, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init); break;
+        case SpmmKernel::SpmvStream8: spmv_stream<T, 8><<<g, 256, 0, s>>>(r, z, rp, col, vals, x, y, row_nnz, neg_init); break;
+        default: BSM_REQUIRE(false, BSM_ERR_INVALID, "SpMV rule chose kernel %d for k = 1", (int)kernel);
+        }
         BSM_HIP_TRY(hipGetLastError());
         return BSM_OK;
     }
     BSM_REQUIRE(!neg_init, BSM_ERR_INVALID, "-0 init only for k = 1");
-    const int variant = spmm_variant();
+    const uint64_t nb = (rows + 3) / 4;  // one row per wave
+    BSM_REQUIRE(nb < (1ull << 32), BSM_ERR_UNSUPPORTED, "too many rows for one launch");
     if constexpr (std::is_same_v<T, double>) {
-        if (k == 32 && variant != 1 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {
-            const uint64_t nb = (rows + 3) / 4;
-            BSM_REQUIRE(nb < (1ull << 32), BSM_ERR_UNSUPPORTED, "too many rows for one launch");
-            auto X2 = reinterpret_cast<const double2*>(x);
-            auto Y2 = reinterpret_cast<double2*>(y);
-            const int64_t r = (int64_t)rows;
-            // short rows on average: four rows per wave (variants 5/6 force it)
-            const bool short_rows = nnz <= SHORT_ROW_AVG * rows;
-            if (variant == 5 || variant == 6 || (variant == 0 && short_rows)) {
-                const uint64_t nb4 = (rows + 15) / 16;
-                static const char* pm = getenv("BSM_SPMM_PROBE_MASK");
-                if (pm)
-                    spmm_k32_f64_rows4<4, true><<<(unsigned)nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz,
-                                                                              (uint32_t)strtoul(pm, nullptr, 10));
-                else if (variant == 6)
-                    spmm_k32_f64_rows4<2><<<(unsigned)nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
-                else
-                    spmm_k32_f64_rows4<4><<<(unsigned)nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
-                BSM_HIP_TRY(hipGetLastError());
-                return BSM_OK;
-            }
-            if (variant == 2)
-                spmm_k32_f64<4, false><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
-            else if (variant == 4)
-                spmm_k32_f64<8, true><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
+        auto X2 = reinterpret_cast<const double2*>(x);  // 16-byte aligned: the rule chose a k32 kernel
+        auto Y2 = reinterpret_cast<double2*>(y);
+        const unsigned nb4 = (unsigned)((rows + 15) / 16);  // four rows per wave
+        switch (kernel) {
+        case SpmmKernel::K32Rows4U4:
+        case SpmmKernel::K32Rows4U2: {
+            static const char* pm = getenv("BSM_SPMM_PROBE_MASK");  // measurement only, wrong results
+            if (pm)
+                spmm_k32_f64_rows4<4, true><<<nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz,
+                                                                (uint32_t)strtoul(pm, nullptr, 10));
+            else if (kernel == SpmmKernel::K32Rows4U2)
+                spmm_k32_f64_rows4<2><<<nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
             else
-                spmm_k32_f64<4, true><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
+                spmm_k32_f64_rows4<4><<<nb4, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
             BSM_HIP_TRY(hipGetLastError());
             return BSM_OK;
         }
+        case SpmmKernel::K32Wave4:
+            spmm_k32_f64<4, false><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
+            BSM_HIP_TRY(hipGetLastError());
+            return BSM_OK;
+        case SpmmKernel::K32Wave8Pipe:
+            spmm_k32_f64<8, true><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
+            BSM_HIP_TRY(hipGetLastError());
+            return BSM_OK;
+        case SpmmKernel::K32Wave4Pipe:
+            spmm_k32_f64<4, true><<<(unsigned)nb, 256, 0, s>>>(r, rp, col, vals, X2, Y2, row_nnz);
+            BSM_HIP_TRY(hipGetLastError());
+            return BSM_OK;
+        default: break;
+        }
     }
-    const uint64_t blocks = (rows + 3) / 4;
-    BSM_REQUIRE(blocks < (1ull << 32), BSM_ERR_UNSUPPORTED, "too many rows for one launch");
     const int ki = (int)k;
-    const dim3 g((unsigned)blocks), b(256);
-    if (k <= 2) spmm_rowwave<T, 2, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
-    else if (k <= 4) spmm_rowwave<T, 4, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
-    else if (k <= 8) spmm_rowwave<T, 8, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
-    else if (k <= 16) spmm_rowwave<T, 16, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
-    else if (k <= 32) spmm_rowwave<T, 32, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
-    else spmm_rowwave<T, 64, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz);
+    const dim3 g((unsigned)nb), b(256);
+    switch (kernel) {
+    case SpmmKernel::RowWave2_4: spmm_rowwave<T, 2, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    case SpmmKernel::RowWave4_4: spmm_rowwave<T, 4, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    case SpmmKernel::RowWave8_4: spmm_rowwave<T, 8, 4><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    case SpmmKernel::RowWave16_8: spmm_rowwave<T, 16, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    case SpmmKernel::RowWave32_8: spmm_rowwave<T, 32, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    case SpmmKernel::RowWave64_8: spmm_rowwave<T, 64, 8><<<g, b, 0, s>>>(rows, rp, col, vals, ki, x, y, row_nnz); break;
+    default: BSM_REQUIRE(false, BSM_ERR_INVALID, "SpMM rule chose kernel %d for k = %d", (int)kernel, ki);
+    }
     BSM_HIP_TRY(hipGetLastError());
     return BSM_OK;
 }
@@ -1069,7 +1072,6 @@ int launch_spmm(uint64_t rows, uint64_t nnz, const int64_t* rp, const int32_t* c
 // are not associative.
 // ---------------------------------------------------------------------------
 constexpr int64_t SPLIT_CHUNK = 512;    // entries per wave
-constexpr uint64_t SPLIT_MIN_ROW = 8192;  // use the split kernel when some row is longer
 
 template <typename T> struct UnsignedOf;
 template <> struct UnsignedOf<int32_t> { using type = uint32_t; };
@@ -1152,9 +1154,8 @@ __global__ __launch_bounds__(256) void count_row_nnz(int64_t rows, int k, const 
 }
 
 bool spmm_wants_split(int dtype, uint64_t k, uint64_t max_row_len) {
-    if (const char* e = getenv("BSM_SPMM_SPLIT")) return atoi(e) != 0 && k >= 2 &&
-                                                          !(dtype == BSM_F64 || dtype == BSM_F32);
-    return k >= 2 && max_row_len >= SPLIT_MIN_ROW && !(dtype == BSM_F64 || dtype == BSM_F32);
+    const char* e = getenv("BSM_SPMM_SPLIT");
+    return spmm_split_rule(dtype == BSM_F64 || dtype == BSM_F32, k, max_row_len, e != nullptr, e ? atoi(e) : 0);
 }
 
 int spmm_split_dispatch(int dtype, uint64_t rows, uint64_t nnz, const int64_t* rp, const int32_t* col,
@@ -1204,7 +1205,7 @@ int spmm_dispatch(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const
                   int32_t* row_nnz, bool neg_zero_init, hipStream_t s, uint64_t max_row_len) {
     (void)n_cols;
     return dispatch_dtype(dtype, [&]<typename T>() {
-        return launch_spmm<T>(rows, nnz, rp, col, static_cast<const T*>(vals), k,
+        return launch_spmm<T>(dtype, rows, nnz, rp, col, static_cast<const T*>(vals), k,
                               static_cast<const T*>(x), static_cast<T*>(y), row_nnz,
                               neg_zero_init, s, max_row_len);
     });

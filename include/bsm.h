@@ -703,6 +703,28 @@ uint64_t bsm_dev_scan_workspace_bytes(uint64_t n);
 int bsm_dev_spmm(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz,
                  const int64_t* row_ptr, const int32_t* col, const void* vals, uint64_t k,
                  const void* x, void* y, int32_t* row_nnz, void* stream);
+/* Which kernel bsm_dev_spmm launches for these arguments under the
+ * environment as it is now (BSM_SPMV_VARIANT, BSM_SPMV_ITEMS,
+ * BSM_SPMM_VARIANT); diagnostic, launches nothing. Only the addresses of x
+ * and y are looked at (16-byte alignment). max_row_len: the longest row, or
+ * UINT64_MAX when unknown, which is what bsm_dev_spmm itself passes; the
+ * handle calls (bsm_csr_mul_dense, bsm_csr_mul_vector) pass the analysed
+ * value. Returns 0 for rows == 0 (no launch), -1 for an unknown dtype, else:
+ *  1 spmv_thread<12>     2 spmv_wave<8>     3 spmv_wave<12>   4 spmv_wave<16>
+ *  5 spmv_rows<16>       6 spmv_stream<2>   7 spmv_stream<4>  8 spmv_stream<8>
+ *  9 k32_f64_rows4<4>   10 k32_f64_rows4<2>
+ * 11 k32_f64<4>         12 k32_f64<4,pipe> 13 k32_f64<8,pipe>
+ * 14 rowwave<2,4>  15 rowwave<4,4>  16 rowwave<8,4>  17 rowwave<16,8>
+ * 18 rowwave<32,8> 19 rowwave<64,8>
+ * (enum class SpmmKernel, csrc/spmm_rule.hpp). The tiled copy, the column
+ * panels and the integer split schedule are chosen before this rule. */
+int bsm_dev_spmm_kernel(int dtype, uint64_t rows, uint64_t nnz, uint64_t k, uint64_t max_row_len,
+                        const void* x, const void* y);
+/* Whether bsm_csr_mul_dense replaces that kernel by the nnz-balanced integer
+ * schedule (spmm_split_int) for a matrix of this scalar type and longest row
+ * and k right-hand columns, under BSM_SPMM_SPLIT as it is now: the very
+ * function the handle path asks. 1 / 0, -1 for an unknown dtype. */
+int bsm_dev_spmm_wants_split(int dtype, uint64_t k, uint64_t max_row_len);
 /* Width of the column-panel plan bsm_csr_mul_dense has cached for this
  * handle and uses (0 = one pass); diagnostic (see bsm_dev_spmm_plan). */
 int bsm_csr_panel_cols(const bsm_csr* m, uint64_t* panel_cols);

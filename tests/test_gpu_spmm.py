@@ -358,6 +358,78 @@ def test_transpose_random(orc, dtype):
     assert_csr_bits(t, *orc.transpose(rows, n_cols, rp, ci, v))
 
 
+def edge_values(rng, dt, n):
+    if dt.kind == "f":
+        return rng.uniform(-2, 2, n).astype(dt)
+    info = np.iinfo(dt)
+    return rng.integers(info.min, info.max, n, dtype=dt, endpoint=True)
+
+
+@pytest.mark.parametrize("cols", [1, 2, 3, 256, 257, 65536, 65537, 2**24 + 1])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_transpose_column_count_edges(orc, dtype, cols):
+    """transpose_dispatch sorts the columns as radix keys of end_bit bits,
+    computed from cols: at cols = 2^b + 1 the last column, 2^b, is the one key
+    that needs bit b. Entries in column 0 and in the last column, drawn from
+    few distinct columns (heavy duplicates inside a row and across rows, whose
+    order the stable sort keeps; most columns empty), empty rows, unsorted
+    rows, every scalar type."""
+    dt = np.dtype(dtype)
+    rng = np.random.default_rng([32, DTYPES.index(dtype), cols])
+    rows = 150
+    lens = rng.integers(0, 40, rows)
+    lens[[0, 7, 8, 9, rows - 1]] = 0
+    lens[1] = 5
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    nnz = int(rp[-1])
+    distinct = np.unique(np.concatenate([[0, cols - 1, cols // 2, (cols - 1) // 2, cols - 1 - min(cols - 1, 1)],
+                                         rng.integers(0, cols, 6)]))
+    ci = distinct[rng.integers(0, len(distinct), nnz)].astype(np.uint64)
+    ci[:2] = [cols - 1, 0]  # row 1 (the first with entries): last column before column 0
+    v = edge_values(rng, dt, nnz)
+    assert lens[1] >= 2 and (ci == 0).sum() > 1 and (ci == cols - 1).sum() > 1
+    t = Csr.from_csr_arrays((rows, cols), rp, ci, v).transpose()
+    assert t.dims.as_tuple() == (cols, rows)
+    assert_csr_bits(t, *orc.transpose(rows, cols, rp, ci, v))
+
+
+@pytest.mark.parametrize("cols", [1, 257])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_transpose_no_entries(orc, dtype, cols):
+    dt = np.dtype(dtype)
+    rp, ci, v = np.zeros(5, np.uint64), np.zeros(0, np.uint64), np.zeros(0, dt)
+    t = Csr.from_csr_arrays((4, cols), rp, ci, v).transpose()
+    assert t.dims.as_tuple() == (cols, 4) and t.get_nnz() == 0
+    assert_csr_bits(t, *orc.transpose(4, cols, rp, ci, v))
+
+
+def test_mul_vector_unsorted_rows_double_transpose(orc):
+    """mul_vector of a matrix with unsorted rows sorts every row stably first
+    (two transposes) and sums in ascending column order: a few thousand rows
+    with repeated columns, values and x from uniform(-2, 2), so the sums pass
+    through mixed signs and any other order changes bits."""
+    rng = np.random.default_rng(33)
+    rows, n_cols = 3001, 257
+    lens = rng.integers(0, 31, rows)
+    lens[[0, 100, 101, rows - 1]] = 0
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    nnz = int(rp[-1])
+    ci = rng.integers(0, n_cols, nnz).astype(np.uint64)
+    ci[rng.integers(0, nnz, 200)] = n_cols - 1
+    v, x = rng.uniform(-2, 2, nnz), rng.uniform(-2, 2, n_cols)
+    srt = ci[np.lexsort((ci, np.repeat(np.arange(rows), lens)))]
+    assert np.count_nonzero(srt != ci) > nnz // 2  # unsorted indeed
+    exp = orc.mul_vector(rows, n_cols, rp, ci, v, x)
+    as_stored = orc.mul_dense(rows, n_cols, rp, ci, v, [x])[2]
+    assert len(as_stored) == np.count_nonzero(lens)  # no row sums to zero
+    assert np.count_nonzero(exp[lens > 0].view(np.uint64) != as_stored.view(np.uint64)) > rows // 3
+    out = np.full(rows, 7.0)
+    Csr.from_csr_arrays((rows, n_cols), rp, ci, v).mul_vector(x, out)
+    bad = np.nonzero(out.view(np.uint64) != exp.view(np.uint64))[0]
+    assert bad.size == 0, f"{bad.size} rows differ, first {bad[:5]}"
+    assert np.all(np.signbit(out[lens == 0]))  # empty rows: -0.0
+
+
 def test_transpose_duplicates_stable(orc):
     a = Csr.new((3, 3), np.int32)
     for val, r, c in [(1, 0, 2), (2, 0, 2), (3, 1, 0), (4, 2, 2), (5, 2, 0)]:
