@@ -50,6 +50,8 @@ BSM_ERR_HIP = 5
 BSM_ERR_OOM = 6
 BSM_ERR_UNSUPPORTED = 7
 BSM_TILED_ANY_PADDING = 1
+BSM_SDDMM_ALL = 0
+BSM_SDDMM_SYM_LOWER = 1
 BSM_ERR_NO_DEVICE = 8
 BSM_ERR_OUT_OF_BOUNDS = 9
 BSM_ERR_COMM = 10
@@ -134,6 +136,10 @@ SIGNATURES = [
     ("bsm_dev_nd_factor_solve_sparse", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_refactor_partial", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_refactor_since", _int, [_vp, _vp, _vp, _vp]),
+    ("bsm_nd_factor_pattern_info", _int, [_vp, _u64p, ctypes.POINTER(_int)]),
+    ("bsm_dev_nd_factor_refactor_values", _int, [_vp, _int, _u64, _vp, _vp]),
+    ("bsm_dev_nd_factor_inv_pattern", _int, [_vp, _u64, _vp, _vp]),
+    ("bsm_dev_nd_factor_sddmm", _int, [_vp, _int, _u64, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),
@@ -144,6 +150,7 @@ SIGNATURES = [
     ("bsm_dev_gen_insert_stream", _int, [_int, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_dev_csr_from_inserts", _int, [_int, _u64, _u64, _u64, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     ("bsm_dev_scan_workspace_bytes", _u64, [_u64]),
+    ("bsm_dev_sddmm", _int, [_int, _int, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_dev_spmm", _int, [_int, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_csr_panel_cols", _int, [_vp, _u64p]),
     ("bsm_dev_spmm_kernel", _int, [_int, _u64, _u64, _u64, _u64, _vp, _vp]),

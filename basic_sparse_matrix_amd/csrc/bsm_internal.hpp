@@ -443,6 +443,20 @@ int nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uint64_t* c
 // (active fronts, fronts in the plan, changed entries). Synchronous on s.
 int nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a, uint64_t nc,
                                const uint64_t* rows, const uint64_t* cols, uint64_t* info, hipStream_t s);
+// The differentiable solve's pieces. The sampled dense-dense
+// product on a CSR pattern (kernels_sddmm.hip; mode: BSM_SDDMM_*; async on s):
+// the checks of dtype, mode, k and squareness are its own.
+int sddmm_dispatch(int dtype, int mode, uint64_t rows, uint64_t cols, uint64_t nnz, const int64_t* rp,
+                   const int32_t* col, uint64_t k, const void* u, const void* v, void* out, hipStream_t s);
+// BSM_SDDMM_SYM_LOWER on the factor's kept pattern (async on s)
+int nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t k, const void* u, const void* v, void* out,
+                    hipStream_t s);
+// nd_factor_refactor on the kept pattern with nnz device values of `dtype` in
+// its storage order: no upload, no pattern comparison. Synchronous on s.
+int nd_factor_refactor_values(bsm_nd_factor* f, int dtype, uint64_t nnz, const void* vals_dev, hipStream_t s);
+// nd_factor_selinv's Z read out at every stored entry of the kept pattern
+// (f->nnz values of f's dtype on the device). Synchronous on s.
+int nd_factor_inv_pattern(const bsm_nd_factor* f, void* out_dev, hipStream_t s);
 // mixed precision on a kept factor (kernels_refine.hip)
 // n float values into the other float dtype, round-to-nearest (async on s)
 int convert_values(int src_dtype, int dst_dtype, uint64_t n, const void* src, void* dst, hipStream_t s);

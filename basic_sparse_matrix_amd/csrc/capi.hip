@@ -1407,6 +1407,50 @@ int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream)
     return nd_factor_selinv(f, diag, 0, nullptr, nullptr, nullptr, &n_miss, &first, static_cast<hipStream_t>(stream));
 }
 
+// ---- the differentiable solve's device calls ----
+static int nd_factor_on_device(const bsm_nd_factor* f) {
+    int dev = 0;
+    BSM_TRY(current_device(&dev));
+    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
+                dev);
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t nnz, uint64_t k, const void* u, const void* v,
+                            void* out, void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(f->n == 0 || f->nnz == 0 || k == 0 || (u && v && out), BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(nnz == f->nnz, BSM_ERR_INVALID,
+                "nd factor sddmm: nnz differs (%llu given, the factored pattern has %llu entries)",
+                (unsigned long long)nnz, (unsigned long long)f->nnz);
+    if (f->n > 0 && f->nnz > 0 && k > 0) BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_sddmm(f, dtype, k, u, v, out, static_cast<hipStream_t>(stream));
+}
+
+int bsm_dev_nd_factor_refactor_values(bsm_nd_factor* f, int dtype, uint64_t nnz, const void* vals, void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(f->n == 0 || f->nnz == 0 || vals, BSM_ERR_INVALID, "null argument");
+    BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_refactor_values(f, dtype, nnz, vals, static_cast<hipStream_t>(stream));
+}
+
+int bsm_dev_nd_factor_inv_pattern(const bsm_nd_factor* f, uint64_t nnz, void* out, void* stream) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(f->n == 0 || f->nnz == 0 || out, BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(nnz == f->nnz, BSM_ERR_INVALID,
+                "nd factor inv_pattern: nnz differs (%llu given, the factored pattern has %llu entries)",
+                (unsigned long long)nnz, (unsigned long long)f->nnz);
+    BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_inv_pattern(f, out, static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_pattern_info(const bsm_nd_factor* f, uint64_t* nnz, int* src_dtype) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    if (nnz) *nnz = f->nnz;
+    if (src_dtype) *src_dtype = f->src_dtype;
+    return BSM_OK;
+}
+
 int bsm_nd_factor_updown(bsm_nd_factor* f, int sign, uint64_t k, const uint64_t* col_ptr, const uint64_t* rows,
                          const void* vals) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
@@ -1615,6 +1659,12 @@ int bsm_dev_spmm(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz, const 
     if (k == 0) return BSM_OK;
     return spmm_dispatch(dtype, rows, n_cols, nnz, row_ptr, col, vals, k, x, y, row_nnz, false,
                          static_cast<hipStream_t>(stream));
+}
+
+int bsm_dev_sddmm(int dtype, int mode, uint64_t rows, uint64_t cols, uint64_t nnz, const int64_t* row_ptr,
+                  const int32_t* col, uint64_t k, const void* u, const void* v, void* out, void* stream) {
+    BSM_REQUIRE(rows == 0 || nnz == 0 || k == 0 || (row_ptr && col && u && v && out), BSM_ERR_INVALID, "null argument");
+    return sddmm_dispatch(dtype, mode, rows, cols, nnz, row_ptr, col, k, u, v, out, static_cast<hipStream_t>(stream));
 }
 
 int bsm_dev_spmm_kernel(int dtype, uint64_t rows, uint64_t nnz, uint64_t k, uint64_t max_row_len, const void* x,

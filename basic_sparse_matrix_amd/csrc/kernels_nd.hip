@@ -2896,10 +2896,30 @@ __global__ __launch_bounds__(256) void nd_selinv_diag_out(int64_t n, const int32
     diag[perm[q]] = Z[nd.foff + c * nd.ld + c];
 }
 
-// vals[e] = Z[rows[e]][cols[e]] (A's order, either triangle; both indices < n):
-// the front owning the lower of the two new indices, the higher one a pivot
-// row of it or found among its front rows. A pair outside the pattern of
-// L + L^T: counted in miss[0], the first such e in miss[1], vals[e] = 0.
+// Z at new indices (p, q), either triangle: the front owning the lower of the
+// two, the higher one a pivot row of it or found among its front rows. *hit is
+// false (and the value 0) for a pair outside the pattern of L + L^T.
+template <typename T>
+__device__ __forceinline__ T nd_selinv_at(int64_t p, int64_t q, const int32_t* __restrict__ owner,
+                                          const NdDev* __restrict__ nodes, const int32_t* __restrict__ st,
+                                          const T* __restrict__ Z, bool* hit) {
+    const int64_t lo = p < q ? p : q, hi = p < q ? q : p;
+    const NdDev& nd = nodes[owner[lo]];
+    const int64_t c = lo - nd.start;
+    int64_t r = hi - nd.start;
+    *hit = true;
+    if (hi >= nd.start + nd.np) {
+        const int32_t* const fs = st + nd.st_off;
+        const int32_t a = lower_bound_i32(fs, nd.m, hi);
+        *hit = a < nd.m && fs[a] == hi;
+        r = nd.np_pad + a;
+    }
+    return *hit ? Z[nd.foff + c * nd.ld + r] : (T)0;
+}
+
+// vals[e] = Z[rows[e]][cols[e]] (A's order, either triangle; both indices < n).
+// A pair outside the pattern of L + L^T: counted in miss[0], the first such e
+// in miss[1], vals[e] = 0.
 template <typename T>
 __global__ __launch_bounds__(256) void nd_selinv_lookup(int64_t nq, const uint64_t* __restrict__ rows,
                                                         const uint64_t* __restrict__ cols,
@@ -2910,33 +2930,48 @@ __global__ __launch_bounds__(256) void nd_selinv_lookup(int64_t nq, const uint64
                                                         unsigned long long* __restrict__ miss) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nq) return;
-    const int64_t p = pinv[rows[e]], q = pinv[cols[e]];
-    const int64_t lo = p < q ? p : q, hi = p < q ? q : p;
-    const NdDev& nd = nodes[owner[lo]];
-    const int64_t c = lo - nd.start;
-    int64_t r = hi - nd.start;
-    bool hit = true;
-    if (hi >= nd.start + nd.np) {
-        const int32_t* const fs = st + nd.st_off;
-        const int32_t a = lower_bound_i32(fs, nd.m, hi);
-        hit = a < nd.m && fs[a] == hi;
-        r = nd.np_pad + a;
-    }
+    bool hit;
+    const T z = nd_selinv_at<T>(pinv[rows[e]], pinv[cols[e]], owner, nodes, st, Z, &hit);
     if (!hit) {
         atomicAdd(&miss[0], 1ull);
         atomicMin(&miss[1], (unsigned long long)e);
     }
-    vals[e] = hit ? Z[nd.foff + c * nd.ld + r] : (T)0;
+    vals[e] = z;
+}
+
+// The same read-out over a CSR pattern (bsm_dev_nd_factor_inv_pattern):
+// vals[e] = Z[i][col[e]] with i the row of entry e, found by bisection of rp
+// (n + 1 entries). Every stored entry of the factored pattern lies in the
+// fronts, so there is no miss to count.
+template <typename T>
+__global__ __launch_bounds__(256) void nd_selinv_lookup_csr(int64_t n, int64_t nnz, const int64_t* __restrict__ rp,
+                                                            const int32_t* __restrict__ col,
+                                                            const int32_t* __restrict__ pinv,
+                                                            const int32_t* __restrict__ owner,
+                                                            const NdDev* __restrict__ nodes,
+                                                            const int32_t* __restrict__ st, const T* __restrict__ Z,
+                                                            T* __restrict__ vals) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nnz) return;
+    int64_t lo = 0, hi = n - 1;  // the smallest row with rp[row + 1] > e
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (rp[mid + 1] > e) hi = mid;
+        else lo = mid + 1;
+    }
+    bool hit;
+    vals[e] = nd_selinv_at<T>(pinv[lo], pinv[col[e]], owner, nodes, st, Z, &hit);
 }
 
 // The selected inverse of a kept factor: Z and the panels for the call (not
 // the handle's bytes, not the cache's budget), the levels top-down, then the
-// read-outs into diag_dev (n values, or null) and vals_dev (nq pairs). The
+// read-outs into diag_dev (n values, or null), vals_dev (nq pairs) and
+// pattern_dev (f.nnz values in the kept pattern's storage order, or null). The
 // caller holds f.mu; f's storage is only read.
 template <typename T>
 int nd_factor_selinv_t(const bsm_nd_factor& f, void* diag_dev, uint64_t nq, const uint64_t* rows_dev,
                        const uint64_t* cols_dev, void* vals_dev, uint64_t* n_miss, uint64_t* first_miss,
-                       hipStream_t s) {
+                       hipStream_t s, void* pattern_dev = nullptr) {
     stage_reset(s);
     const int64_t N = (int64_t)f.n;
     const NdOpts opt = nd_options();
@@ -2985,6 +3020,13 @@ int nd_factor_selinv_t(const bsm_nd_factor& f, void* diag_dev, uint64_t nq, cons
     stage_mark("nd_selinv", s);
     if (diag_dev) {
         nd_selinv_diag_out<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, p.owner, p.nodes, p.perm, Z, static_cast<T*>(diag_dev));
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    if (pattern_dev && f.nnz > 0) {
+        const char* const pb = f.pattern->as<char>();
+        nd_selinv_lookup_csr<T><<<nd_blocks((int64_t)f.nnz, 256), 256, 0, s>>>(
+            N, (int64_t)f.nnz, (const int64_t*)pb, (const int32_t*)(pb + nd_pattern_rp_bytes(N)), p.pinv, p.owner,
+            p.nodes, p.st, Z, static_cast<T*>(pattern_dev));
         BSM_HIP_TRY(hipGetLastError());
     }
     unsigned long long h[2] = {0, ~0ull};
@@ -4066,6 +4108,25 @@ int nd_factor_selinv(const bsm_nd_factor* f, void* diag_dev, uint64_t nq, const 
                : nd_factor_selinv_t<float>(*f, diag_dev, nq, rows_dev, cols_dev, vals_dev, n_miss, first_miss, s);
 }
 
+int nd_factor_inv_pattern(const bsm_nd_factor* f, void* out_dev, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(f->mu);
+    BSM_REQUIRE(f->valid, BSM_ERR_INVALID, "nd factor: factor holds no values; refactor first");
+    if (f->n == 0 || f->nnz == 0) return BSM_OK;
+    uint64_t n_miss = 0, first = 0;
+    return f->dtype == BSM_F64
+               ? nd_factor_selinv_t<double>(*f, nullptr, 0, nullptr, nullptr, nullptr, &n_miss, &first, s, out_dev)
+               : nd_factor_selinv_t<float>(*f, nullptr, 0, nullptr, nullptr, nullptr, &n_miss, &first, s, out_dev);
+}
+
+int nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t k, const void* u, const void* v, void* out,
+                    hipStream_t s) {
+    if (f->n == 0 || f->nnz == 0)  // its checks of dtype and k, no launch
+        return sddmm_dispatch(dtype, BSM_SDDMM_SYM_LOWER, 0, 0, 0, nullptr, nullptr, k, u, v, out, s);
+    const char* const pb = f->pattern->as<char>();  // immutable for the handle's life: no lock
+    return sddmm_dispatch(dtype, BSM_SDDMM_SYM_LOWER, f->n, f->n, f->nnz, (const int64_t*)pb,
+                          (const int32_t*)(pb + nd_pattern_rp_bytes((int64_t)f->n)), k, u, v, out, s);
+}
+
 int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s) {
     BSM_REQUIRE(a->rows < ((uint64_t)1 << 31), BSM_ERR_UNSUPPORTED, "solve nd: n >= 2^31");
     BSM_REQUIRE(a->dtype == BSM_F64 || a->dtype == BSM_F32, BSM_ERR_INVALID, "solve: f32/f64 only");
@@ -4107,6 +4168,31 @@ int nd_factor_refactor(bsm_nd_factor* f, const bsm_csr* a, hipStream_t s) {
                 (unsigned long long)a->nnz, (unsigned long long)f->nnz);
     std::lock_guard<std::mutex> lk(f->mu);
     return f->dtype == BSM_F64 ? nd_factor_refactor_t<double>(a, *f, s) : nd_factor_refactor_t<float>(a, *f, s);
+}
+
+int nd_factor_refactor_values(bsm_nd_factor* f, int dtype, uint64_t nnz, const void* vals_dev, hipStream_t s) {
+    BSM_REQUIRE(dtype == f->src_dtype, BSM_ERR_INVALID,
+                "nd factor refactor: dtype differs from the factored matrix's (%s was factored, the values are %s)",
+                f->src_dtype == BSM_F64 ? "f64" : "f32",
+                dtype == BSM_F64 ? "f64" : dtype == BSM_F32 ? "f32" : "not a float");
+    if (f->n == 0) return BSM_OK;
+    BSM_REQUIRE(nnz == f->nnz, BSM_ERR_INVALID,
+                "nd factor refactor: nnz differs (%llu values given, the factored matrix had %llu entries)",
+                (unsigned long long)nnz, (unsigned long long)f->nnz);
+    bsm_csr a;  // a view: the kept pattern with the caller's values (nothing is owned, nothing cached on it)
+    char* const pb = f->pattern->as<char>();
+    a.dtype = dtype;
+    a.device = f->device;
+    a.rows = a.cols = f->n;
+    a.nnz = f->nnz;
+    a.row_ptr = (int64_t*)pb;
+    a.col = (int32_t*)(pb + nd_pattern_rp_bytes((int64_t)f->n));
+    a.vals = const_cast<void*>(vals_dev);
+    std::lock_guard<std::mutex> lk(f->mu);
+    stage_reset(s);
+    const auto pc = std::static_pointer_cast<NdCached>(f->plan);
+    return f->dtype == BSM_F64 ? nd_factor_numeric_t<double>(&a, *f, *pc, nd_options(), s)
+                               : nd_factor_numeric_t<float>(&a, *f, *pc, nd_options(), s);
 }
 
 // refactor's checks of a matrix against the handle, with its messages

@@ -400,6 +400,145 @@ def nd_factor_inv_diag(factor, out: torch.Tensor | None = None, *, stream=None) 
     return out
 
 
+SDDMM_MODES = {"all": _lib.BSM_SDDMM_ALL, "sym_lower": _lib.BSM_SDDMM_SYM_LOWER}
+_NP_OF_TORCH = {torch.float64: np.dtype(np.float64), torch.float32: np.dtype(np.float32)}
+
+
+def _sddmm_operands(what: str, u: torch.Tensor, v: torch.Tensor, out, nnz: int, rows: int, cols: int, want=None):
+    """The SDDMM's host-side checks of U, V and out (dtype, shape, contiguity,
+    device, in that order); ``(n,)`` counts as k = 1. Returns ``(k, out)``."""
+    want = u.dtype if want is None else want
+    if want not in _NP_OF_TORCH:
+        raise TypeError(f"{what}: u is {u.dtype}, needs float32 or float64")
+    out = torch.empty((nnz,), dtype=want, device=u.device) if out is None else out
+    for name, t in (("u", u), ("v", v), ("out", out)):
+        if t.dtype != want:
+            raise TypeError(f"{what}: {name} is {t.dtype}, needs {want}")
+    for name, t, n in (("u", u, rows), ("v", v, cols)):
+        if t.dim() not in (1, 2) or t.shape[0] != n:
+            raise ValueError(f"{what}: {name} must be ({n},) or ({n}, k), got {tuple(t.shape)}")
+    ku, kv = (t.shape[1] if t.dim() == 2 else 1 for t in (u, v))
+    if ku != kv:
+        raise ValueError(f"{what}: u has {ku} columns, v {kv}")
+    if ku == 0:
+        raise ValueError(f"{what}: k == 0 (a dot product of no terms)")
+    if out.dim() != 1 or out.shape[0] != nnz:
+        raise ValueError(f"{what}: out must be ({nnz},), got {tuple(out.shape)}")
+    for name, t in (("u", u), ("v", v), ("out", out)):
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} is not on the device")
+    if v.device != u.device or out.device != u.device:
+        raise ValueError(f"{what}: u is on {u.device}, v on {v.device}, out on {out.device}")
+    return ku, out
+
+
+def sddmm(row_ptr: torch.Tensor, col: torch.Tensor, u: torch.Tensor, v: torch.Tensor, mode: str = "all",
+          out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """The sampled dense-dense product on a CSR pattern (``bsm_dev_sddmm``):
+    ``out[p] = dot(u[i, :], v[j, :])`` for every stored entry ``p = (i, j)``.
+    ``row_ptr`` is int64 ``(rows + 1,)`` and ``col`` int32 ``(nnz,)`` as
+    ``DeviceCsrBlock`` holds them; ``u`` is row-major ``(rows, k)``, ``v``
+    ``(cols, k)`` (``(n,)`` counts as k = 1), float32 or float64, contiguous,
+    on one device; ``out`` is ``(nnz,)`` of that dtype and defaults to a new
+    tensor. ``mode="sym_lower"`` (square patterns) gives ``dot(u_i, v_j) +
+    dot(u_j, v_i)`` below the diagonal, ``dot(u_i, v_i)`` on it and ``+0.0``
+    above. The dot's order depends on k alone: the same bits on every launch.
+    Asynchronous on ``stream``."""
+    if mode not in SDDMM_MODES:
+        raise ValueError(f"sddmm: mode must be one of {sorted(SDDMM_MODES)}, got {mode!r}")
+    for name, t, dt in (("row_ptr", row_ptr, torch.int64), ("col", col, torch.int32)):
+        if t.dtype != dt:
+            raise TypeError(f"sddmm: {name} is {t.dtype}, needs {dt}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"sddmm: {name} must be contiguous and 1-D, got {tuple(t.shape)}")
+    if row_ptr.shape[0] < 1:
+        raise ValueError("sddmm: row_ptr needs rows + 1 entries")
+    rows, nnz, cols = row_ptr.shape[0] - 1, col.shape[0], v.shape[0] if v.dim() else 0
+    if mode == "sym_lower" and rows != cols:
+        raise ValueError(f"sddmm: mode='sym_lower' needs a square pattern, got {rows} x {cols}")
+    k, out = _sddmm_operands("sddmm", u, v, out, nnz, rows, cols)
+    if row_ptr.device != u.device or col.device != u.device:
+        raise ValueError(f"sddmm: the pattern is on {row_ptr.device} / {col.device}, u on {u.device}")
+    _lib.check(_lib.require_device().bsm_dev_sddmm(_lib.DTYPE_CODES[_NP_OF_TORCH[u.dtype]], SDDMM_MODES[mode], rows,
+                                                   cols, nnz, _p(row_ptr), _p(col), k, _p(u), _p(v), _p(out),
+                                                   _stream(stream)))
+    return out
+
+
+def nd_factor_sddmm(factor, u: torch.Tensor, v: torch.Tensor, out: torch.Tensor | None = None, *,
+                    stream=None) -> torch.Tensor:
+    """:func:`sddmm` with ``mode="sym_lower"`` on the pattern a kept factor
+    (``solver.NdFactor``) was made from (``bsm_dev_nd_factor_sddmm``): ``u``
+    and ``v`` are ``(n,)`` or row-major ``(n, k)`` of one float dtype, ``out``
+    is ``(pattern_nnz,)`` in the pattern's storage order. With ``u = Λ`` and
+    ``v = x`` its negative is the gradient of a solve with respect to the
+    matrix's stored values. Asynchronous on ``stream``."""
+    from .sparse import _raise_for
+
+    nnz = factor.pattern_nnz
+    k, out = _sddmm_operands("nd_factor_sddmm", u, v, out, nnz, factor.n, factor.n)
+    h = factor._h()
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_sddmm(h, _lib.DTYPE_CODES[_NP_OF_TORCH[u.dtype]], nnz, k,
+                                                             _p(u), _p(v), _p(out), _stream(stream)))
+    return out
+
+
+def nd_factor_refactor_values(factor, vals: torch.Tensor, *, stream=None) -> None:
+    """``NdFactor.refactor`` from values that are already in HBM
+    (``bsm_dev_nd_factor_refactor_values``): ``vals`` is 1-D, contiguous, on
+    the factor's device, of the FACTORED MATRIX's dtype (``src_dtype``), with
+    ``pattern_nnz`` entries in the factored pattern's storage order. No
+    upload, no pattern comparison; the factor has the bits ``refactor`` gives
+    on a ``Csr`` with these values, and its errors. Runs on ``stream`` and
+    returns after the factorisation's status word is read back. The factor
+    records ``(vals.data_ptr(), vals._version, its rewrite count)`` for
+    ``autograd``'s ``refactor=False`` and keeps a reference to ``vals`` until
+    its next rewrite, so that the address cannot pass to another tensor."""
+    from .sparse import _raise_for
+
+    want = TORCH_DT[np.dtype(factor.src_dtype)]
+    if vals.dtype != want:
+        raise TypeError(f"nd_factor_refactor_values: vals is {vals.dtype}, the factored matrix is {factor.src_dtype}")
+    nnz = factor.pattern_nnz
+    if vals.dim() != 1 or vals.shape[0] != nnz or not vals.is_contiguous():
+        raise ValueError(f"nd_factor_refactor_values: vals must be contiguous, ({nnz},), got {tuple(vals.shape)}")
+    if not vals.is_cuda:
+        raise ValueError("nd_factor_refactor_values: vals is not on the device")
+    h = factor._h()
+    factor._bump_epoch()  # the factor is rewritten, also when the call fails
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_refactor_values(
+        h, _lib.DTYPE_CODES[np.dtype(factor.src_dtype)], nnz, _p(vals), _stream(stream)))
+    factor._vals_key = (vals.data_ptr(), vals._version, factor._epoch)
+    factor._vals_ref = vals  # keeps the storage, so no other tensor can take its address while the record stands
+
+
+def nd_factor_inv_pattern(factor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
+    """``(S^-1)[i, j]`` at every stored entry of the factored pattern, both
+    triangles, into a device tensor (``bsm_dev_nd_factor_inv_pattern``):
+    ``(pattern_nnz,)``, contiguous, of the factor's dtype, in the pattern's
+    storage order; ``out`` defaults to a new tensor. The bits of
+    ``NdFactor.inv_on(a).v`` without the host round trip. Runs on ``stream``
+    and returns after it has drained."""
+    from .sparse import _raise_for
+
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    nnz = factor.pattern_nnz
+    if out is None:
+        factor._h()
+        out = torch.empty((nnz,), dtype=want, device="cuda")
+    if out.dtype != want:
+        raise TypeError(f"nd_factor_inv_pattern: out is {out.dtype}, the factor is {factor.dtype}")
+    if out.dim() != 1 or out.shape[0] != nnz or not out.is_contiguous():
+        raise ValueError(f"nd_factor_inv_pattern: out must be contiguous, ({nnz},), got {tuple(out.shape)}")
+    if not out.is_cuda:
+        raise ValueError("nd_factor_inv_pattern: out is not on the device")
+    h = factor._h()
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_inv_pattern(h, nnz, _p(out), _stream(stream)))
+    return out
+
+
 class Compactor:
     """Dense Y -> output Csr (the zero-dropping insert of sparse.rs:229) with
     preallocated worst-case buffers, so a timed step allocates nothing."""

@@ -267,11 +267,14 @@ class NdFactor:
     solve with f64 residuals and reports its backward error, ``solve_pcg``
     uses the factor as the preconditioner of conjugate gradients; the factor's
     dtype may be chosen apart from the matrix's
-    (``cholesky_nd(a, factor_dtype=...)``). The handle owns its
+    (``cholesky_nd(a, factor_dtype=...)``). ``refactor_values`` refactors from
+    a device tensor of values, and ``autograd.nd_solve`` / ``autograd.nd_logdet``
+    differentiate the solve and the log-determinant. The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
-    __slots__ = ("handle", "n", "dtype", "src_dtype")
+    __slots__ = ("handle", "n", "dtype", "src_dtype", "_pattern_nnz", "_epoch", "_vals_key", "_vals_ref",
+                 "_grad_weights")
 
     def __init__(self, handle: int, src_dtype=None):
         lib = _lib.load()
@@ -282,6 +285,32 @@ class NdFactor:
         self.dtype = _lib.CODE_DTYPES[d.value]
         # the factored matrix's dtype (update / downdate take W in it)
         self.src_dtype = self.dtype if src_dtype is None else np.dtype(src_dtype)
+        nnz = ctypes.c_uint64()
+        _lib.check(lib.bsm_nd_factor_pattern_info(handle, ctypes.byref(nnz), None))
+        self._pattern_nnz = nnz.value
+        self._epoch = 0  # counts the calls that rewrite the factor (autograd.py: a backward after one is refused)
+        self._vals_key = None  # refactor_values' record of the device values this is the factor of
+        self._vals_ref = None  # ... and those values, kept so that their address stays theirs
+        self._grad_weights = None  # autograd.nd_logdet's 0 / 1 / 2 per stored entry, built once
+
+    @property
+    def pattern_nnz(self) -> int:
+        """Stored entries of the factored pattern (both triangles): the length
+        of ``refactor_values``' ``vals`` and of ``device.nd_factor_inv_pattern``'s
+        result (``bsm_nd_factor_pattern_info``). It never changes."""
+        return self._pattern_nnz
+
+    def _bump_epoch(self) -> None:
+        self._epoch = getattr(self, "_epoch", 0) + 1
+        self._vals_key = self._vals_ref = None
+
+    def refactor_values(self, vals) -> None:
+        """``refactor`` from a device tensor of values in the factored
+        pattern's storage order: ``device.nd_factor_refactor_values(self,
+        vals)``, which needs torch."""
+        from .device import nd_factor_refactor_values
+
+        nd_factor_refactor_values(self, vals)
 
     def _h(self) -> int:
         if not self.handle:
@@ -472,6 +501,7 @@ class NdFactor:
         _check_factorable(a, "NdFactor.refactor")
         h = self._h()
         dev = a._device()
+        self._bump_epoch()
         _raise_for(_lib.require_device().bsm_nd_factor_refactor(h, dev.handle))
 
     def refactor_partial(self, a: Csr, rows=None, cols=None, *, since: Csr | None = None) -> PartialInfo:
@@ -512,6 +542,7 @@ class NdFactor:
             _check_factorable(since, what)
             if since.dtype != a.dtype:
                 raise TypeError(f"{what}: since is Csr<{since.dtype}>, a is Csr<{a.dtype}>")
+            self._bump_epoch()
             _raise_for(lib().bsm_nd_factor_refactor_since(h, since._device().handle, a._device().handle,
                                                           _lib.ptr(info)))
         else:
@@ -522,6 +553,7 @@ class NdFactor:
             if r.shape[0] != c.shape[0]:
                 raise ValueError(f"{what}: rows has {r.shape[0]} entries, cols {c.shape[0]}")
             nc = r.shape[0]
+            self._bump_epoch()
             _raise_for(lib().bsm_nd_factor_refactor_partial(h, a._device().handle, nc, _lib.ptr(r) if nc else None,
                                                             _lib.ptr(c) if nc else None, _lib.ptr(info)))
         return PartialInfo(int(info[0]), int(info[1]), int(info[2]))
@@ -541,6 +573,7 @@ class NdFactor:
         col_ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=k))]).astype(np.uint64)
         r = np.ascontiguousarray(rows[order])
         vals = np.ascontiguousarray(np.asarray(v, dtype=want)[order])
+        self._bump_epoch()
         _raise_for(_lib.require_device().bsm_nd_factor_updown(h, sign, k, _lib.ptr(col_ptr), _lib.ptr(r),
                                                               _lib.ptr(vals)))
 
@@ -768,6 +801,7 @@ class NdFactor:
         if h and _lib._lib is not None:
             _lib._lib.bsm_nd_factor_free(h)
         self.handle = None
+        self._vals_key = self._vals_ref = self._grad_weights = None  # the device tensors kept for autograd
 
     def __enter__(self) -> "NdFactor":
         return self

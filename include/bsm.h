@@ -656,6 +656,40 @@ int bsm_nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a, uint64_t 
                                    const uint64_t* cols, uint64_t* info);
 int bsm_nd_factor_refactor_since(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a_new, uint64_t* info);
 void bsm_nd_factor_free(bsm_nd_factor* f);
+/* The differentiable solve's pieces: everything a gradient of x = S^-1 b or of
+ * log det S with respect to the stored values needs, with every operand in HBM
+ * on the factor's device and the work on `stream`. "The factored pattern" is
+ * the row_ptr / col of the matrix given to bsm_nd_factor_create(_as), which the
+ * handle keeps; its entries are counted by bsm_nd_factor_pattern_info. This
+ * build's addition.
+ *  - bsm_nd_factor_pattern_info: *nnz = the factored pattern's stored entries
+ *    (both triangles), *src_dtype = the factored matrix's dtype (the factor's
+ *    own is bsm_nd_factor_info's). Either pointer may be NULL. No device use.
+ *  - bsm_dev_nd_factor_refactor_values: bsm_nd_factor_refactor without the
+ *    matrix handle: nnz device values of `dtype` in the factored pattern's
+ *    storage order (entries with col > row are ignored, as ever). No upload and
+ *    no pattern comparison. dtype must be the factored matrix's and nnz the
+ *    pattern's (else BSM_ERR_INVALID, nothing written); an f32 factor of an f64
+ *    matrix converts the values as bsm_nd_factor_refactor does. The factor has
+ *    the bits bsm_nd_factor_refactor gives on a matrix with these values, under
+ *    either pipeline. Values that are not positive definite: its error, the
+ *    handle left without a factor until a later good call. Takes the handle's
+ *    mutex; returns after the status word is read.
+ *  - bsm_dev_nd_factor_inv_pattern: (S^-1)[i, j] at every stored entry of the
+ *    factored pattern, both triangles, nnz values of the FACTOR's dtype in the
+ *    pattern's storage order: bsm_nd_factor_selinv's recursion with a read-out
+ *    over the kept pattern, the same bits as bsm_nd_factor_selinv on those
+ *    pairs. nnz must be the pattern's. Synchronous for `stream`.
+ *  - bsm_dev_nd_factor_sddmm: bsm_dev_sddmm (below) in BSM_SDDMM_SYM_LOWER mode
+ *    on the factored pattern: u and v are ROW-major n x k of `dtype`, out nnz
+ *    values. nnz must be the pattern's. Asynchronous on `stream`.
+ * All four refuse a null handle, and a null array with work to do, before any
+ * device is asked for. */
+int bsm_nd_factor_pattern_info(const bsm_nd_factor* f, uint64_t* nnz, int* src_dtype);
+int bsm_dev_nd_factor_refactor_values(bsm_nd_factor* f, int dtype, uint64_t nnz, const void* vals, void* stream);
+int bsm_dev_nd_factor_inv_pattern(const bsm_nd_factor* f, uint64_t nnz, void* out, void* stream);
+int bsm_dev_nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t nnz, uint64_t k, const void* u, const void* v,
+                            void* out, void* stream);
 /* The cross-handle plan cache of bsm_solve_nd: drop every entry, or read its
  * state (entries, kept numeric bytes, lookups that hit / missed since load).
  * Any pointer may be NULL. This build's addition. */
@@ -703,6 +737,25 @@ uint64_t bsm_dev_scan_workspace_bytes(uint64_t n);
 int bsm_dev_spmm(int dtype, uint64_t rows, uint64_t n_cols, uint64_t nnz,
                  const int64_t* row_ptr, const int32_t* col, const void* vals, uint64_t k,
                  const void* x, void* y, int32_t* row_nnz, void* stream);
+/* The sampled dense-dense product (SDDMM): out[p] for every stored entry
+ * p = (i, j) of a CSR pattern (row_ptr: rows + 1, col: nnz, any column order
+ * inside a row), from ROW-major U (rows x k) and V (cols x k) of dtype
+ * BSM_F32 / BSM_F64; out has nnz values of it and nothing else is written.
+ *   BSM_SDDMM_ALL        out[p] = dot(U[i,:], V[j,:])
+ *   BSM_SDDMM_SYM_LOWER  square patterns: j < i: dot(U[i,:], V[j,:]) +
+ *                        dot(U[j,:], V[i,:]); j == i: dot(U[i,:], V[i,:]);
+ *                        j > i: +0.0
+ * dot has one fixed order that depends on k alone (products rounded, no fma;
+ * for k <= 64 a halving tree of width the smallest power of two >= k, for
+ * k > 64 chunks of 64 columns added in ascending order), so the bits do not
+ * depend on the launch, on nnz or on where an entry sits. No atomics.
+ * rows == 0 or nnz == 0 launches nothing. k == 0, another dtype or mode, or
+ * BSM_SDDMM_SYM_LOWER with rows != cols -> BSM_ERR_INVALID; so is a null
+ * array with work to do. This build's addition. */
+#define BSM_SDDMM_ALL 0
+#define BSM_SDDMM_SYM_LOWER 1
+int bsm_dev_sddmm(int dtype, int mode, uint64_t rows, uint64_t cols, uint64_t nnz, const int64_t* row_ptr,
+                  const int32_t* col, uint64_t k, const void* u, const void* v, void* out, void* stream);
 /* Which kernel bsm_dev_spmm launches for these arguments under the
  * environment as it is now (BSM_SPMV_VARIANT, BSM_SPMV_ITEMS,
  * BSM_SPMM_VARIANT); diagnostic, launches nothing. Only the addresses of x

@@ -180,6 +180,10 @@ def main():
                     help="only the partial refactor record: K seeded stored entries changed and named as one call, "
                          "against refactor in the same session, and one line with an f32 factor "
                          "(profiles/nd_partial_c5.jsonl)")
+    ap.add_argument("--grad", default=None, metavar="K[,K...]",
+                    help="only the differentiable solve's record: refactor_values against refactor, and for each K "
+                         "the solve, the backward's solve, nd_factor_sddmm (with its achieved bytes per second) and "
+                         "inv_pattern, operands in HBM (profiles/nd_grad_c5.jsonl)")
     ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
                     help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
                          "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
@@ -214,6 +218,13 @@ def main():
         with open(os.path.join(ROOT, "profiles", "nd_partial_c5.jsonl"), "a") as out:
             for line in nd_partial_ops(A, B, [int(k) for k in args.partial.split(",")], max(args.reps, 1),
                                        (n, rp, ci, v)):
+                print(json.dumps(line), flush=True)
+                out.write(json.dumps(line) + "\n")
+        return
+    if args.grad:
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "nd_grad_c5.jsonl"), "a") as out:
+            for line in nd_grad_ops(A, [int(k) for k in args.grad.split(",")], (n, rp, ci, v)):
                 print(json.dumps(line), flush=True)
                 out.write(json.dumps(line) + "\n")
         return
@@ -822,6 +833,73 @@ def nd_partial_ops(A, B, ks, reps, pattern):
             for line in lines:
                 if line["config"]["factor_dtype"] == str(np.dtype(fdt)):
                     line["refactor_after_ms"] = med(t_after)
+    return lines
+
+
+def nd_grad_ops(A, ks, pattern):
+    """The differentiable solve's calls on the kept factor,
+    every operand in HBM: refactor_values against refactor(a) on the same
+    matrix, and per K right-hand columns the solve, the backward's solve
+    (another right-hand side), nd_factor_sddmm and, once, inv_pattern (every
+    call's time and stage marks beside the median: its 6 GB allocation of Z
+    stalls now and then). Host wall ms around each call with
+    the device drained before and after (medians of 3 after one warm-up). The SDDMM's line carries the achieved
+    bytes per second over its compulsory traffic: the pattern once
+    (8 (n + 1) + 4 nnz), U and V once each (2 n K es) and out once (nnz es).
+    One JSON line per K, also appended to profiles/nd_grad_c5.jsonl."""
+    import torch
+
+    from basic_sparse_matrix_amd import cholesky_nd, device
+
+    n, rp, ci, v = pattern
+    es = np.dtype(A.dtype).itemsize
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+
+    def timed(fn, reps=3):
+        t = []
+        for _ in range(reps + 1):  # the first call warms the temporaries
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            t.append(time.perf_counter() - t0)
+        return t[1:]
+
+    lines = []
+    vals = torch.tensor(np.ascontiguousarray(v), device="cuda")
+    with cholesky_nd(A) as f:
+        nnz = f.pattern_nnz
+        t_ref = timed(lambda: f.refactor(A))
+        ld_ref = f.logdet()
+        t_val = timed(lambda: device.nd_factor_refactor_values(f, vals))
+        same = f.logdet() == ld_ref
+        z = torch.empty((nnz,), dtype=vals.dtype, device="cuda")
+        _lib.stage_timing(True)  # the selected inverse's marks: its allocation of Z, the recursion, the read-out
+        inv_stages = []
+        t_inv = timed(lambda: (device.nd_factor_inv_pattern(f, out=z), inv_stages.append(_lib.stage_times())))
+        _lib.stage_timing(False)
+        inv_stages = [{k: round(x, 3) for k, x in st.items() if k.startswith("nd_selinv")} for st in inv_stages[1:]]
+        for K in ks:
+            gen = torch.Generator(device="cuda").manual_seed(3000 + K)
+            shape = (n,) if K == 1 else (n, K)
+            b = torch.randn(shape, dtype=vals.dtype, device="cuda", generator=gen)
+            g = torch.randn(shape, dtype=vals.dtype, device="cuda", generator=gen)
+            x, lam, out = torch.empty_like(b), torch.empty_like(b), torch.empty_like(z)
+            t_solve = timed(lambda: device.nd_factor_solve(f, b, out=x))
+            t_back = timed(lambda: device.nd_factor_solve(f, g, out=lam))
+            t_sd = timed(lambda: device.nd_factor_sddmm(f, lam, x, out=out))
+            traffic = 8 * (n + 1) + 4 * nnz + 2 * n * K * es + nnz * es
+            lines.append({
+                "metric": "C5 nd factor: the differentiable solve's calls, operands in HBM (host wall ms around "
+                          "each call, device drained, medians of 3)",
+                "config": {"g": int(round(n ** 0.5)), "K": int(K), "dtype": str(np.dtype(A.dtype)), "nnz": int(nnz)},
+                "refactor_ms": med(t_ref), "refactor_values_ms": med(t_val), "refactor_values_same_logdet": bool(same),
+                "solve_ms": med(t_solve), "backward_solve_ms": med(t_back), "sddmm_ms": med(t_sd),
+                "sddmm_compulsory_bytes": int(traffic),
+                "sddmm_gbs": round(traffic / float(np.median(t_sd)) / 1e9, 1),
+                "sddmm_over_backward_solve": round(float(np.median(t_sd)) / float(np.median(t_back)), 4),
+                "inv_pattern_ms": med(t_inv), "inv_pattern_ms_each": [round(1e3 * t, 3) for t in t_inv],
+                "inv_pattern_stages_ms_each": inv_stages})
     return lines
 
 
