@@ -245,7 +245,7 @@ struct bsm_csr {
     // cached row-block x column-panel copy (kernels_tiled.hip), same mutex
     mutable bsm_tiled* tiled = nullptr;
     mutable bool tiled_tried = false;
-    // solve(order="nd")'s plan (kernels_nd.hip): the pattern's ordering, tree
+    // solve(order="nd")'s plan (kernels_nd_plan.hip): the pattern's ordering, tree
     // and device index arrays, built on first use (the pattern is immutable),
     // same mutex; released with the handle
     mutable std::shared_ptr<void> nd_plan;
@@ -400,7 +400,7 @@ int solve_dispatch_full(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_
 int solve_dispatch_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
                            hipStream_t s);
 int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_dev, void* x_dev, hipStream_t s);
-// the kept nd factor (kernels_nd.hip); all synchronous on s. b_dev / x_dev:
+// the kept nd factor (kernels_nd.hip and kernels_nd_*.hip); all synchronous on s. b_dev / x_dev:
 // ROW-major n x k, as solve_dispatch_nd's
 // factor_dtype: BSM_F64 or BSM_F32; where it is not a's, a's values are converted first
 int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s);

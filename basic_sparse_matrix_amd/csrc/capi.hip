@@ -770,8 +770,10 @@ int bsm_csr_upload(int dtype, uint64_t rows, uint64_t cols, uint64_t nnz, const 
     return csr_upload_rows(dtype, 0, rows, cols, row_ptr, col_idx, vals, out, s);
 }
 
-int bsm_csr_from_inserts(int dtype, uint64_t rows, uint64_t cols, uint64_t n, const uint64_t* row,
-                         const uint64_t* col, const void* vals, bsm_csr** out) {
+// n host triplets to the device, then `build` (csr_from_inserts_device's signature) on them
+static int csr_from_host_triplets(decltype(&csr_from_inserts_device) build, int dtype, uint64_t rows, uint64_t cols,
+                                  uint64_t n, const uint64_t* row, const uint64_t* col, const void* vals,
+                                  bsm_csr** out) {
     BSM_REQUIRE(out && (n == 0 || (row && col && vals)), BSM_ERR_INVALID, "null argument");
     const size_t es = dtype_size(dtype);
     BSM_REQUIRE(es, BSM_ERR_INVALID, "unknown dtype %d", dtype);
@@ -786,26 +788,17 @@ int bsm_csr_from_inserts(int dtype, uint64_t rows, uint64_t cols, uint64_t n, co
         BSM_HIP_TRY(hipMemcpyAsync(dc.p, col, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         BSM_HIP_TRY(hipMemcpyAsync(dv.p, vals, n * es, hipMemcpyHostToDevice, s));
     }
-    return csr_from_inserts_device(dtype, rows, cols, n, dr.as<uint64_t>(), dc.as<uint64_t>(), dv.p, out, s);
+    return build(dtype, rows, cols, n, dr.as<uint64_t>(), dc.as<uint64_t>(), dv.p, out, s);
+}
+
+int bsm_csr_from_inserts(int dtype, uint64_t rows, uint64_t cols, uint64_t n, const uint64_t* row,
+                         const uint64_t* col, const void* vals, bsm_csr** out) {
+    return csr_from_host_triplets(csr_from_inserts_device, dtype, rows, cols, n, row, col, vals, out);
 }
 
 int bsm_csr_from_coo(int dtype, uint64_t rows, uint64_t cols, uint64_t n, const uint64_t* row,
                      const uint64_t* col, const void* vals, bsm_csr** out) {
-    BSM_REQUIRE(out && (n == 0 || (row && col && vals)), BSM_ERR_INVALID, "null argument");
-    const size_t es = dtype_size(dtype);
-    BSM_REQUIRE(es, BSM_ERR_INVALID, "unknown dtype %d", dtype);
-    hipStream_t s;
-    BSM_TRY(ctx_stream(&s));
-    DBuf dr, dc, dv;
-    BSM_TRY(dr.alloc((n ? n : 1) * sizeof(uint64_t)));
-    BSM_TRY(dc.alloc((n ? n : 1) * sizeof(uint64_t)));
-    BSM_TRY(dv.alloc((n ? n : 1) * es));
-    if (n) {
-        BSM_HIP_TRY(hipMemcpyAsync(dr.p, row, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        BSM_HIP_TRY(hipMemcpyAsync(dc.p, col, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        BSM_HIP_TRY(hipMemcpyAsync(dv.p, vals, n * es, hipMemcpyHostToDevice, s));
-    }
-    return csr_from_coo_device(dtype, rows, cols, n, dr.as<uint64_t>(), dc.as<uint64_t>(), dv.p, out, s);
+    return csr_from_host_triplets(csr_from_coo_device, dtype, rows, cols, n, row, col, vals, out);
 }
 
 int bsm_dev_csr_from_inserts(int dtype, uint64_t rows, uint64_t cols, uint64_t n, const uint64_t* row,
@@ -1032,7 +1025,9 @@ int bsm_backward_substitution(const bsm_csr* u, uint64_t k, uint64_t n, const vo
     return trsv_host(u, false, k, n, y_cols, x_cols);
 }
 
-int bsm_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols, void* const* x_cols) {
+// solve on host columns, by whichever elimination `dispatch` runs
+static int solve_host(decltype(&solve_dispatch_full) dispatch, const bsm_csr* a, uint64_t k, uint64_t n,
+                      const void* const* b_cols, void* const* x_cols) {
     BSM_REQUIRE(a && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");
     BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
                 "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
@@ -1042,45 +1037,35 @@ int bsm_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_col
     DBuf b, x;
     BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
     BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
-    BSM_TRY(solve_dispatch_full(a, k, n, b.p, x.p, s));
+    BSM_TRY(dispatch(a, k, n, b.p, x.p, s));
     return download_columns(a->dtype, n, k, x.p, x_cols, s);
+}
+
+int bsm_solve(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols, void* const* x_cols) {
+    return solve_host(solve_dispatch_full, a, k, n, b_cols, x_cols);
 }
 
 int bsm_solve_blocked(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols, void* const* x_cols) {
-    BSM_REQUIRE(a && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");
-    BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
-                "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
-    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
-    hipStream_t s;
-    BSM_TRY(ctx_stream(&s));
-    DBuf b, x;
-    BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
-    BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
-    BSM_TRY(solve_dispatch_blocked(a, k, n, b.p, x.p, s));
-    return download_columns(a->dtype, n, k, x.p, x_cols, s);
+    return solve_host(solve_dispatch_blocked, a, k, n, b_cols, x_cols);
 }
 
 int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_cols, void* const* x_cols) {
-    BSM_REQUIRE(a && (k == 0 || (b_cols && x_cols)), BSM_ERR_INVALID, "null argument");
-    BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
-                "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
-    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
-    hipStream_t s;
-    BSM_TRY(ctx_stream(&s));
-    DBuf b, x;
-    BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
-    BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
-    BSM_TRY(solve_dispatch_nd(a, k, n, b.p, x.p, s));
-    return download_columns(a->dtype, n, k, x.p, x_cols, s);
+    return solve_host(solve_dispatch_nd, a, k, n, b_cols, x_cols);
 }
 
 // ---- the kept nd factor ----------------------------------------------------
-// the calling thread's stream, on the device the factor lives on
-static int nd_factor_stream(const bsm_nd_factor* f, hipStream_t* s) {
+// the calling thread is on the device the factor lives on
+static int nd_factor_on_device(const bsm_nd_factor* f) {
     int dev = 0;
     BSM_TRY(current_device(&dev));
     BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
                 dev);
+    return BSM_OK;
+}
+
+// the calling thread's stream, on that device
+static int nd_factor_stream(const bsm_nd_factor* f, hipStream_t* s) {
+    BSM_TRY(nd_factor_on_device(f));
     return ctx_stream(s);
 }
 
@@ -1125,16 +1110,14 @@ static int refine_check(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, co
 int bsm_dev_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
                                     uint32_t max_iter, double tol, uint32_t* iters, double* berr, void* stream) {
     BSM_TRY(refine_check(f, a, k, b, x, tol));
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     return nd_refine_solve(f, a, k, b, x, max_iter, tol, iters, berr, static_cast<hipStream_t>(stream));
 }
 
-int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
-                                const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
-                                uint32_t* iters, double* berr) {
+// the refined and the pcg solve on host columns (pcg: flags too, else flags stays untouched)
+static int refine_host(bool pcg, const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                       const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol, uint32_t* iters,
+                       double* berr, uint32_t* flags) {
     BSM_TRY(refine_check(f, a, k, b_cols, x_cols, tol));
     for (uint64_t j = 0; j < k && n && f->n; ++j)
         BSM_REQUIRE(b_cols[j] && x_cols[j], BSM_ERR_INVALID, "null column pointer %llu", (unsigned long long)j);
@@ -1146,52 +1129,37 @@ int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64
     DBuf b, x;
     BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
     BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
-    std::vector<uint32_t> it(k);
+    std::vector<uint32_t> it(k), fl(pcg ? k : 0);
     std::vector<double> be(k);
-    BSM_TRY(nd_refine_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), s));
+    BSM_TRY(pcg ? nd_pcg_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), fl.data(), s)
+                : nd_refine_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), s));
     BSM_TRY(download_columns(a->dtype, n, k, x.p, x_cols, s));
     for (uint64_t j = 0; j < k; ++j) {  // the outputs are written together, after everything that can fail
         if (iters) iters[j] = it[j];
         if (berr) berr[j] = be[j];
+        if (pcg && flags) flags[j] = fl[j];
     }
     return BSM_OK;
+}
+
+int bsm_nd_factor_solve_refined(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
+                                const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
+                                uint32_t* iters, double* berr) {
+    return refine_host(false, f, a, k, n, b_cols, x_cols, max_iter, tol, iters, berr, nullptr);
 }
 
 int bsm_dev_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, const void* b, void* x,
                                 uint32_t max_iter, double tol, uint32_t* iters, double* berr, uint32_t* flags,
                                 void* stream) {
     BSM_TRY(refine_check(f, a, k, b, x, tol));
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     return nd_pcg_solve(f, a, k, b, x, max_iter, tol, iters, berr, flags, static_cast<hipStream_t>(stream));
 }
 
 int bsm_nd_factor_solve_pcg(const bsm_nd_factor* f, const bsm_csr* a, uint64_t k, uint64_t n,
                             const void* const* b_cols, void* const* x_cols, uint32_t max_iter, double tol,
                             uint32_t* iters, double* berr, uint32_t* flags) {
-    BSM_TRY(refine_check(f, a, k, b_cols, x_cols, tol));
-    for (uint64_t j = 0; j < k && n && f->n; ++j)
-        BSM_REQUIRE(b_cols[j] && x_cols[j], BSM_ERR_INVALID, "null column pointer %llu", (unsigned long long)j);
-    BSM_REQUIRE(f->n == n, BSM_ERR_PANIC,
-                "solve: b has %llu rows but A has %llu (index out of bounds in the reference)", (unsigned long long)n,
-                (unsigned long long)f->n);
-    hipStream_t s;
-    BSM_TRY(nd_factor_stream(f, &s));
-    DBuf b, x;
-    BSM_TRY(upload_columns(a->dtype, n, k, b_cols, b, s));
-    BSM_TRY(x.alloc(n * k * dtype_size(a->dtype)));
-    std::vector<uint32_t> it(k), fl(k);
-    std::vector<double> be(k);
-    BSM_TRY(nd_pcg_solve(f, a, k, b.p, x.p, max_iter, tol, it.data(), be.data(), fl.data(), s));
-    BSM_TRY(download_columns(a->dtype, n, k, x.p, x_cols, s));
-    for (uint64_t j = 0; j < k; ++j) {  // the outputs are written together, after everything that can fail
-        if (iters) iters[j] = it[j];
-        if (berr) berr[j] = be[j];
-        if (flags) flags[j] = fl[j];
-    }
-    return BSM_OK;
+    return refine_host(true, f, a, k, n, b_cols, x_cols, max_iter, tol, iters, berr, flags);
 }
 
 // eigsh's checks, all before any device is asked for; *ncv_use is the basis size in use
@@ -1213,38 +1181,8 @@ int bsm_dev_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t n
                             uint32_t* info, void* stream) {
     uint64_t m = 0;
     BSM_TRY(eigsh_check(f, a, nev, block, ncv, tol, lam, resid, &m));
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     return nd_eigsh(f, a, nev, block, m, tol, seed, v0, lam, vecs, resid, info, static_cast<hipStream_t>(stream));
-}
-
-int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
-                        double tol, uint64_t seed, const void* const* v0_cols, double* lam, void* const* vec_cols,
-                        double* resid, uint32_t* info) {
-    uint64_t m = 0;
-    BSM_TRY(eigsh_check(f, a, nev, block, ncv, tol, lam, resid, &m));
-    const uint64_t n = f->n;
-    for (uint64_t j = 0; j < block && n && v0_cols; ++j)
-        BSM_REQUIRE(v0_cols[j], BSM_ERR_INVALID, "null column pointer %llu (v0)", (unsigned long long)j);
-    for (uint64_t j = 0; j < nev && n && vec_cols; ++j)
-        BSM_REQUIRE(vec_cols[j], BSM_ERR_INVALID, "null column pointer %llu (the vectors)", (unsigned long long)j);
-    hipStream_t s;
-    BSM_TRY(nd_factor_stream(f, &s));
-    DBuf v0, vec;
-    if (v0_cols && n) BSM_TRY(upload_columns(a->dtype, n, block, v0_cols, v0, s));
-    if (vec_cols && n) BSM_TRY(vec.alloc(n * nev * dtype_size(a->dtype)));
-    std::vector<double> l(nev), r(nev);
-    uint32_t inf[4] = {0, 0, 0, 0};
-    BSM_TRY(nd_eigsh(f, a, nev, block, m, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s));
-    if (vec.p) BSM_TRY(download_columns(a->dtype, n, nev, vec.p, vec_cols, s));
-    for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
-        lam[i] = l[i];
-        resid[i] = r[i];
-    }
-    for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
-    return BSM_OK;
 }
 
 // eigsh_gen's checks: eigsh_check's, then the mass matrix against a
@@ -1267,20 +1205,18 @@ int bsm_dev_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const 
     if (!m) return bsm_dev_nd_factor_eigsh(f, a, nev, block, ncv, tol, seed, v0, lam, vecs, resid, info, stream);
     uint64_t nc = 0;
     BSM_TRY(eigsh_gen_check(f, a, m, nev, block, ncv, tol, lam, resid, &nc));
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     return nd_eigsh_gen(f, a, m, nev, block, nc, tol, seed, v0, lam, vecs, resid, info,
                         static_cast<hipStream_t>(stream));
 }
 
-int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
-                            uint64_t ncv, double tol, uint64_t seed, const void* const* v0_cols, double* lam,
-                            void* const* vec_cols, double* resid, uint32_t* info) {
-    if (!m) return bsm_nd_factor_eigsh(f, a, nev, block, ncv, tol, seed, v0_cols, lam, vec_cols, resid, info);
+// eigsh on host columns; m: the mass matrix, null for the standard problem
+static int eigsh_host(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
+                      uint64_t ncv, double tol, uint64_t seed, const void* const* v0_cols, double* lam,
+                      void* const* vec_cols, double* resid, uint32_t* info) {
     uint64_t nc = 0;
-    BSM_TRY(eigsh_gen_check(f, a, m, nev, block, ncv, tol, lam, resid, &nc));
+    BSM_TRY(m ? eigsh_gen_check(f, a, m, nev, block, ncv, tol, lam, resid, &nc)
+              : eigsh_check(f, a, nev, block, ncv, tol, lam, resid, &nc));
     const uint64_t n = f->n;
     for (uint64_t j = 0; j < block && n && v0_cols; ++j)
         BSM_REQUIRE(v0_cols[j], BSM_ERR_INVALID, "null column pointer %llu (v0)", (unsigned long long)j);
@@ -1293,7 +1229,8 @@ int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_
     if (vec_cols && n) BSM_TRY(vec.alloc(n * nev * dtype_size(a->dtype)));
     std::vector<double> l(nev), r(nev);
     uint32_t inf[4] = {0, 0, 0, 0};
-    BSM_TRY(nd_eigsh_gen(f, a, m, nev, block, nc, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s));
+    BSM_TRY(m ? nd_eigsh_gen(f, a, m, nev, block, nc, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s)
+              : nd_eigsh(f, a, nev, block, nc, tol, seed, v0.p, l.data(), vec.p, r.data(), inf, s));
     if (vec.p) BSM_TRY(download_columns(a->dtype, n, nev, vec.p, vec_cols, s));
     for (uint64_t i = 0; i < nev; ++i) {  // the outputs are written together, after everything that can fail
         lam[i] = l[i];
@@ -1301,6 +1238,18 @@ int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_
     }
     for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];
     return BSM_OK;
+}
+
+int bsm_nd_factor_eigsh(const bsm_nd_factor* f, const bsm_csr* a, uint64_t nev, uint64_t block, uint64_t ncv,
+                        double tol, uint64_t seed, const void* const* v0_cols, double* lam, void* const* vec_cols,
+                        double* resid, uint32_t* info) {
+    return eigsh_host(f, a, nullptr, nev, block, ncv, tol, seed, v0_cols, lam, vec_cols, resid, info);
+}
+
+int bsm_nd_factor_eigsh_gen(const bsm_nd_factor* f, const bsm_csr* a, const bsm_csr* m, uint64_t nev, uint64_t block,
+                            uint64_t ncv, double tol, uint64_t seed, const void* const* v0_cols, double* lam,
+                            void* const* vec_cols, double* resid, uint32_t* info) {
+    return eigsh_host(f, a, m, nev, block, ncv, tol, seed, v0_cols, lam, vec_cols, resid, info);
 }
 
 int bsm_nd_factor_solve_system(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* const* b_cols,
@@ -1354,10 +1303,7 @@ int bsm_nd_factor_logdet(const bsm_nd_factor* f, double* logdet) {
 int bsm_dev_nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, const void* b, void* x, void* stream) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
     BSM_REQUIRE(f->n * k == 0 || (b && x), BSM_ERR_INVALID, "null argument");
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     return nd_factor_solve(f, system, k, f->n, b, x, static_cast<hipStream_t>(stream));
 }
 
@@ -1399,23 +1345,12 @@ int bsm_nd_factor_selinv(const bsm_nd_factor* f, void* diag, uint64_t nq, const 
 int bsm_dev_nd_factor_inv_diag(const bsm_nd_factor* f, void* diag, void* stream) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
     BSM_REQUIRE(f->n == 0 || diag, BSM_ERR_INVALID, "null argument");
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     uint64_t n_miss = 0, first = 0;
     return nd_factor_selinv(f, diag, 0, nullptr, nullptr, nullptr, &n_miss, &first, static_cast<hipStream_t>(stream));
 }
 
 // ---- the differentiable solve's device calls ----
-static int nd_factor_on_device(const bsm_nd_factor* f) {
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
-    return BSM_OK;
-}
-
 int bsm_dev_nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t nnz, uint64_t k, const void* u, const void* v,
                             void* out, void* stream) {
     BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
@@ -1588,10 +1523,7 @@ int bsm_dev_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uin
         for (int i = 0; i < 4 && info; ++i) info[i] = 0;
         return BSM_OK;
     }
-    int dev = 0;
-    BSM_TRY(current_device(&dev));
-    BSM_REQUIRE(dev == f->device, BSM_ERR_INVALID, "nd factor: made on device %d, called on device %d", f->device,
-                dev);
+    BSM_TRY(nd_factor_on_device(f));
     uint32_t inf[4] = {0, 0, 0, 0};
     BSM_TRY(nd_factor_solve_sparse(f, k, col_ptr, rows, vals, nq, xrows, x, inf, static_cast<hipStream_t>(stream)));
     for (int i = 0; i < 4 && info; ++i) info[i] = inf[i];

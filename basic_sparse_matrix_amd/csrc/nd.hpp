@@ -1,6 +1,6 @@
 // nd.hpp -- nested-dissection analysis for solve(order="nd") (host C++).
 //
-// The plan of the multifrontal solve (kernels_nd.hip): a fill-reducing
+// The plan of the multifrontal solve (kernels_nd_plan.hip): a fill-reducing
 // permutation from recursive graph bisection (BFS level-set separators) and
 // its separator tree, each node a dense front. Pure host code: no HIP here,
 // so the CPU tests drive it through bsm_nd_analyse.

@@ -1,5 +1,5 @@
 // partial_rule.hpp -- the launch plan of a partial refactor of a kept factor
-// (bsm_nd_factor_refactor_partial, kernels_nd.hip). Given the
+// (bsm_nd_factor_refactor_partial, kernels_nd_partial.hip). Given the
 // active fronts (reach_rule.hpp: the paths from the changed entries' fronts to
 // the roots, in (level, node) order), every level that occurs re-runs nd_factor
 // on the active fronts' tasks alone, in the plan's own order. A front of nt

@@ -1,6 +1,6 @@
 // reach_rule.hpp -- which fronts a solve with a sparse right-hand side and
 // selected solution rows has to visit (bsm_nd_factor_solve_sparse,
-// kernels_nd.hip). On the separator tree (a forest: every
+// kernels_nd_sparse.hip). On the separator tree (a forest: every
 // node has a parent or is a root, at most two children kid0 / kid1, a level =
 // its height, children on lower levels than their parent) the set reached from
 // some start nodes is the union of their paths to the roots:

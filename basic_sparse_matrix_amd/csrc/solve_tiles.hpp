@@ -1,6 +1,6 @@
 // solve_tiles.hpp -- device helpers shared by the blocked band solver
 // (kernels_solve.hip) and the nested-dissection multifrontal solver
-// (kernels_nd.hip): write-through hand-offs, DPP row broadcasts, and the
+// (kernels_nd*.hip): write-through hand-offs, DPP row broadcasts, and the
 // 64 x 64 tile operations on f64 MFMA (factor + inverse of a diagonal tile,
 // tile products). Included inside namespace bsm { namespace { ... } }.
 #pragma once

@@ -1,5 +1,5 @@
 // updown_rule.hpp -- the scalar rule of the rank-k update and downdate of a
-// kept factor (bsm_nd_factor_updown, kernels_nd.hip): the
+// kept factor (bsm_nd_factor_updown, kernels_nd_updown.hip): the
 // column-by-column method (Gill, Golub, Murray, Saunders, method C1) for
 // L L^T + sigma w w^T, sigma = +1 or -1. At pivot j
 //     d = L_jj;  r = sqrt(d^2 + sigma w_j^2);  c = r / d;  s = w_j / d;  L_jj = r

@@ -1,6 +1,6 @@
 """GPU tests of solve(..., order="nd") (bsm_solve_nd): x = A^-1 b
 (src/lib.rs:11-24) by a multifrontal Cholesky of P A P^T, P a
-nested-dissection order (csrc/nd_order.cpp, csrc/kernels_nd.hip). Another
+nested-dissection order (csrc/nd_order.cpp, csrc/kernels_nd*.hip). Another
 elimination order, so not bit-exact; the bar is BASELINE.json's f64
 tolerance, 1e-6 relative against the reference-order result (the band
 oracle, pinned to the reference's goldens). Tighter bounds where the systems
