@@ -12,31 +12,10 @@
 #include <cstring>
 #include <vector>
 
-#include "bsm.hpp"
-#include "../../oracle/bsm_oracle.h"
+#include "nd_test.hpp"
 
 using bsm::Csr;
 using bsm::Dense;
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        ++g_checks;                                                        \
-        if (!(cond)) {                                                     \
-            ++g_fail;                                                      \
-            std::fprintf(stderr, "  CHECK failed: %s (line %d)\n", #cond, __LINE__); \
-        }                                                                  \
-    } while (0)
-
-static Csr<double> poisson(uint64_t g) {
-    const uint64_t n = g * g;
-    std::vector<uint64_t> rp(n + 1), ci(5 * n);
-    std::vector<double> v(5 * n);
-    const uint64_t nnz = orc_gen_poisson2d(g, rp.data(), ci.data(), v.data());
-    ci.resize(nnz);
-    v.resize(nnz);
-    return Csr<double>::from_csr_arrays({n, n}, {rp.begin(), rp.end()}, {ci.begin(), ci.end()}, v);
-}
 
 static void run_gpu() {
     const uint64_t g = 11, n = g * g;
@@ -83,25 +62,12 @@ static void run_gpu() {
     CHECK(refused);
 }
 
+static void touch_device() {
+    const auto f = bsm::cholesky_nd_as<float>(poisson(4));
+    (void)f.eigsh(poisson(4), 2);
+}
+
 int main(int argc, char** argv) {
-    if (argc > 1 && std::strcmp(argv[1], "--expect-no-device") == 0) {
-        bool dev_err = false;
-        try {
-            const auto f = bsm::cholesky_nd_as<float>(poisson(4));
-            (void)f.eigsh(poisson(4), 2);
-        } catch (const bsm::DeviceError&) {
-            dev_err = true;
-        } catch (...) {
-        }
-        std::printf("%s eigsh (DeviceError without a GPU: no CPU fallback)\n", dev_err ? "PASS" : "FAIL");
-        return dev_err ? 0 : 1;
-    }
-    try {
-        run_gpu();
-    } catch (const std::exception& e) {
-        ++g_fail;
-        std::fprintf(stderr, "  EXCEPTION: %s\n", e.what());
-    }
-    std::printf("summary: %d failed, %d checks\n", g_fail, g_checks);
-    return g_fail ? 1 : 0;
+    return nd_test_main(argc, argv, run_gpu, touch_device,
+                        "eigsh (DeviceError without a GPU: no CPU fallback)");
 }

@@ -15,31 +15,10 @@
 #include <cstring>
 #include <vector>
 
-#include "bsm.hpp"
-#include "../../oracle/bsm_oracle.h"
+#include "nd_test.hpp"
 
 using bsm::Csr;
 using bsm::Dense;
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        ++g_checks;                                                        \
-        if (!(cond)) {                                                     \
-            ++g_fail;                                                      \
-            std::fprintf(stderr, "  CHECK failed: %s (line %d)\n", #cond, __LINE__); \
-        }                                                                  \
-    } while (0)
-
-static Csr<double> poisson(uint64_t g) {
-    const uint64_t n = g * g;
-    std::vector<uint64_t> rp(n + 1), ci(5 * n);
-    std::vector<double> v(5 * n);
-    const uint64_t nnz = orc_gen_poisson2d(g, rp.data(), ci.data(), v.data());
-    ci.resize(nnz);
-    v.resize(nnz);
-    return Csr<double>::from_csr_arrays({n, n}, {rp.begin(), rp.end()}, {ci.begin(), ci.end()}, v);
-}
 
 // kron(M1, M1), rows and columns ascending: the values 16/36, 4/36 and 1/36 as Python's np.kron(m1, m1) rounds them
 static Csr<double> consistent_mass(uint64_t g) {
@@ -133,28 +112,13 @@ static void run_gpu() {
     CHECK(refused);
 }
 
+static void touch_device() {
+    const auto f = bsm::cholesky_nd_as<float>(poisson(4));
+    (void)f.eigsh_gen(poisson(4), consistent_mass(4), 2);
+}
+
 int main(int argc, char** argv) {
     args_without_device();
-    if (argc > 1 && std::strcmp(argv[1], "--expect-no-device") == 0) {
-        bool dev_err = false;
-        try {
-            const auto f = bsm::cholesky_nd_as<float>(poisson(4));
-            (void)f.eigsh_gen(poisson(4), consistent_mass(4), 2);
-        } catch (const bsm::DeviceError&) {
-            dev_err = true;
-        } catch (...) {
-        }
-        const bool ok = dev_err && g_fail == 0;
-        std::printf("%s eigsh_gen (argument errors without a device; DeviceError without a GPU: no CPU fallback)\n",
-                    ok ? "PASS" : "FAIL");
-        return ok ? 0 : 1;
-    }
-    try {
-        run_gpu();
-    } catch (const std::exception& e) {
-        ++g_fail;
-        std::fprintf(stderr, "  EXCEPTION: %s\n", e.what());
-    }
-    std::printf("summary: %d failed, %d checks\n", g_fail, g_checks);
-    return g_fail ? 1 : 0;
+    return nd_test_main(argc, argv, run_gpu, touch_device,
+                        "eigsh_gen (argument errors without a device; DeviceError without a GPU: no CPU fallback)");
 }

@@ -9,36 +9,20 @@
 #include <cstring>
 #include <vector>
 
-#include "bsm.hpp"
-#include "../../oracle/bsm_oracle.h"
+#include "nd_test.hpp"
 
 using bsm::Csr;
 using bsm::Dense;
 using bsm::NdSystem;
 
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        ++g_checks;                                                        \
-        if (!(cond)) {                                                     \
-            ++g_fail;                                                      \
-            std::fprintf(stderr, "  CHECK failed: %s (line %d)\n", #cond, __LINE__); \
-        }                                                                  \
-    } while (0)
-
 // scale 1: the Poisson matrix A; otherwise D A D with d_i = 1 + (i % 7) / 8 (SPD with A)
 static Csr<double> poisson(uint64_t g, bool scaled) {
-    const uint64_t n = g * g;
-    std::vector<uint64_t> rp(n + 1), ci(5 * n);
-    std::vector<double> v(5 * n);
-    const uint64_t nnz = orc_gen_poisson2d(g, rp.data(), ci.data(), v.data());
-    ci.resize(nnz);
-    v.resize(nnz);
+    Grid a(g);
     if (scaled)
-        for (uint64_t i = 0; i < n; ++i)
-            for (uint64_t e = rp[i]; e < rp[i + 1]; ++e)
-                v[e] *= (1.0 + (double)(i % 7) / 8.0) * (1.0 + (double)(ci[e] % 7) / 8.0);
-    return Csr<double>::from_csr_arrays({n, n}, {rp.begin(), rp.end()}, {ci.begin(), ci.end()}, v);
+        for (uint64_t i = 0; i < a.n; ++i)
+            for (uint64_t e = a.rp[i]; e < a.rp[i + 1]; ++e)
+                a.v[e] *= (1.0 + (double)(i % 7) / 8.0) * (1.0 + (double)(a.ci[e] % 7) / 8.0);
+    return a.csr();
 }
 
 static bool same_cols(const Dense<double>& x, const Dense<double>& y, uint64_t k, uint64_t n) {
@@ -115,26 +99,13 @@ static void run_gpu() {
     }
 }
 
+static void touch_device() {
+    bsm::NdFactor<double> f(poisson(4, false));
+    f.refactor(poisson(4, true));
+    (void)f.logdet();
+}
+
 int main(int argc, char** argv) {
-    if (argc > 1 && std::strcmp(argv[1], "--expect-no-device") == 0) {
-        bool dev_err = false;
-        try {
-            bsm::NdFactor<double> f(poisson(4, false));
-            f.refactor(poisson(4, true));
-            (void)f.logdet();
-        } catch (const bsm::DeviceError&) {
-            dev_err = true;
-        } catch (...) {
-        }
-        std::printf("%s NdFactor (DeviceError without a GPU: no CPU fallback)\n", dev_err ? "PASS" : "FAIL");
-        return dev_err ? 0 : 1;
-    }
-    try {
-        run_gpu();
-    } catch (const std::exception& e) {
-        ++g_fail;
-        std::fprintf(stderr, "  EXCEPTION: %s\n", e.what());
-    }
-    std::printf("summary: %d failed, %d checks\n", g_fail, g_checks);
-    return g_fail ? 1 : 0;
+    return nd_test_main(argc, argv, run_gpu, touch_device,
+                        "NdFactor (DeviceError without a GPU: no CPU fallback)");
 }

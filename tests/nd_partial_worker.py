@@ -18,22 +18,23 @@ import numpy as np  # noqa: E402
 import test_gpu_nd_partial_refactor as t  # noqa: E402
 
 from basic_sparse_matrix_amd import cholesky_nd  # noqa: E402
+from nd_support import dense_matrix, dense_system, same_bits  # noqa: E402
 
 
 def main():
     name = sys.argv[1]
-    n, s, _, _ = t._system(name)
+    n, s, _, _ = dense_system(name)
     g = t.groups(name)
     equal, finite, fronts, expected, total = True, True, [], [], 0
     for src, fdt in t.DTYPES:
-        with cholesky_nd(t.matrix(s, src), factor_dtype=fdt) as f:
+        with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
             cur = s
             for gname in ("leaf-diagonal", "two-leaves", "separator", "seeded-17"):
                 pairs = g[gname]
                 cur = t.changed(cur, pairs)
-                info = f.refactor_partial(t.matrix(cur, src), *t.rc(pairs))
+                info = f.refactor_partial(dense_matrix(cur, src), *t.rc(pairs))
                 got, want = t.bits(f, name), t.fresh_bits(cur, name, src, fdt)
-                equal = equal and all(t.same_bits(x, y) for x, y in zip(got, want))
+                equal = equal and all(same_bits(x, y) for x, y in zip(got, want))
                 finite = finite and all(np.isfinite(x).all() for x in got)
                 fronts.append(info.fronts)
                 expected.append(len(t.reach(name, t.start_vertices(name, pairs))))

@@ -3,47 +3,21 @@
 header; on the GPU, Poisson g = 11 under BSM_ND_LEAF=8 with an f32 factor of a
 Csr<double>, refined, and the printed x, iters and berr against Python's
 NdFactor.solve_refined bit for bit; without a GPU, the factorisation throws
-bsm::DeviceError (no CPU fallback). The build recipe is test_cpp_nd_selinv.py's."""
+bsm::DeviceError (no CPU fallback)."""
 
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "basic_sparse_matrix_amd", "lib")
-ORC = os.path.join(ROOT, "oracle", "build")
-SRC = os.path.join(ROOT, "tests", "cpp", "test_nd_refine.cpp")
-EXE = os.path.join(ROOT, "tests", "cpp", "build", "test_nd_refine")
+from cpp_support import build_mirror_program, expect_no_device
 
-
-def _build():
-    if not (os.path.exists(os.path.join(LIB, "libbsm_hip.so")) and os.path.exists(os.path.join(ORC, "libbsm_oracle.so"))):
-        pytest.skip("libbsm_hip.so / libbsm_oracle.so not built (run __graft_entry__.build())")
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no C++ compiler")
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    cmd = [cxx, "-std=c++20", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), SRC,
-           "-L", LIB, "-lbsm_hip", "-L", ORC, "-lbsm_oracle", f"-Wl,-rpath,{LIB}", f"-Wl,-rpath,{ORC}",
-           "-Wl,-rpath-link,/opt/rocm/lib", "-o", EXE]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return EXE
+SRC = "test_nd_refine.cpp"
 
 
 def test_cpp_nd_refine_no_cpu_fallback():
-    try:
-        import torch
-
-        if torch.cuda.is_available():
-            pytest.skip("a GPU is present")
-    except ImportError:
-        pass
-    r = subprocess.run([_build(), "--expect-no-device"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    expect_no_device(SRC)
 
 
 @pytest.mark.gpu
@@ -52,7 +26,7 @@ def test_cpp_nd_refine_on_gpu(monkeypatch):
     from oracle import pyoracle as orc
 
     monkeypatch.setenv("BSM_ND_LEAF", "8")
-    r = subprocess.run([_build()], capture_output=True, text=True, timeout=300, env=dict(os.environ))
+    r = subprocess.run([build_mirror_program(SRC)], capture_output=True, text=True, timeout=300, env=dict(os.environ))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 failed" in r.stdout
     g = 11

@@ -1,7 +1,7 @@
 """GPU tests of the smallest eigenpairs by block shift-invert Lanczos on a kept
 nd factor (NdFactor.eigsh, device.nd_factor_eigsh, bsm_nd_factor_eigsh).
 
-The systems restate test_gpu_nd_pcg.py's small generators: one-pivot fronts
+The systems are nd_support.py's, as in test_gpu_nd_pcg.py: one-pivot fronts
 (g5-leaf1), several levels (g11-leaf8), multi-tile fronts (g40-leaf256), fronts
 without pivots (blocks) and an irregular tree (random). The reference is
 np.linalg.eigvalsh / eigh of the dense S (the stored entries with column <=
@@ -29,11 +29,11 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, EigInfo, MatErr, _lib, cholesky_nd
+from nd_support import _scale, assert_same, cols_of, coords, matrix, same_bits, setup, start_block, sym_dense, system
 
 pytestmark = pytest.mark.gpu
 
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+SYSTEMS = ["g5-leaf1", "g11-leaf8", "g40-leaf256", "blocks", "random"]
 NCV = {"g5-leaf1": 24, "g11-leaf8": 60, "g40-leaf256": 60, "blocks": 60, "random": 160}
 F32, F64 = np.float32, np.float64
 NEV, BLOCK = 6, 4
@@ -41,101 +41,19 @@ TOL64, TOL32 = 2.0 ** -26, 2.0 ** -12
 U = 2.0 ** -53
 
 
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, leaf or None), built once."""
-    import scipy.sparse as sp
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
-    if name == "blocks":  # fronts with np == 0
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    if name == "triple":  # three copies of the 7 x 7-grid Poisson matrix: every eigenvalue three times and more
-        g = 7
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, P, P], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    rng = np.random.default_rng(7)  # an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, None
-
-
-@functools.lru_cache(maxsize=None)
-def _coords(name):
-    n, rp, ci, _, _ = _system(name)
-    return np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)
-
-
 @functools.lru_cache(maxsize=None)
 def _truth(name, dtype=F64):
     """(S dense f64 of the values rounded to dtype, ||S||inf, m, eigenvalues ascending, eigenvectors)."""
-    n, _, _, v, _ = _system(name)
-    r, c = _coords(name)
-    low = np.zeros((n, n))
-    keep = c <= r
-    low[r[keep], c[keep]] = v.astype(dtype).astype(np.float64)[keep]
-    S = low + np.tril(low, -1).T
+    S = sym_dense(name, system(name)[3].astype(dtype))
     S.setflags(write=False)
     w, z = np.linalg.eigh(S)
     return S, float(np.abs(S).sum(axis=1).max()), int((S != 0).sum(axis=1).max()), w, z
-
-
-def setup(monkeypatch, name):
-    leaf = _system(name)[4]
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-
-
-def matrix(name, dtype, v=None):
-    """A fresh Csr (a fresh device handle) of the pattern, with the system's values or v."""
-    n, rp, ci, v0, _ = _system(name)
-    return Csr.from_csr_arrays((n, n), rp, ci, np.asarray(v0 if v is None else v).astype(dtype))
-
-
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
 
 
 def parts(lam, y, info):
     return [lam] + (cols_of(y) if y is not None else []) + [info.resid, info.converged,
                                                            np.array([info.steps, info.ncv_used, info.exhausted,
                                                                      info.inexact])]
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
 
 
 def assert_pairs(name, lam, y, info, tol, what, dtype=F64, count=NEV):
@@ -160,35 +78,7 @@ def assert_pairs(name, lam, y, info, tol, what, dtype=F64, count=NEV):
     assert orth <= 2 * tol
 
 
-# ---- the start block, restated: bsm_hash(seed, row, column, 6) mapped to [-1, 1) ------------
-
-M64 = (1 << 64) - 1
-
-
-def _mix64(z):
-    z = (z + 0x9E3779B97F4A7C15) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-def start_block(n, block, seed=0, dtype=F64):
-    out = np.zeros((n, block))
-    h0 = _mix64(seed ^ ((6 * 0xD1B54A32D192ED03) & M64))
-    for r in range(n):
-        hr = _mix64(h0 ^ r)
-        for c in range(block):
-            h = _mix64(hr ^ ((c * 0x9E3779B97F4A7C15) & M64))
-            out[r, c] = 2.0 * ((0.5 + (h >> 11) * 2.0 ** -53) - 1.0)
-    return out.astype(dtype)
-
-
 # ---- the loop, emulated: np.linalg.cholesky in the factor's dtype stands for the factor -------
-
-
-def _scale(v):
-    m = np.abs(v).max()
-    return 2.0 ** np.floor(np.log2(m)) if m > 0 and np.isfinite(m) else 1.0
 
 
 @functools.lru_cache(maxsize=None)
@@ -276,7 +166,7 @@ def _default_run(name, fdtype):
 def test_smallest_pairs_of_an_f64_matrix(monkeypatch, name, fdtype):
     setup(monkeypatch, name)
     lam, y, info = _default_run(name, fdtype)
-    assert y.dtype == np.dtype(F64) and y.get_dims().cols == NEV and y.get_dims().rows == _system(name)[0]
+    assert y.dtype == np.dtype(F64) and y.get_dims().cols == NEV and y.get_dims().rows == system(name)[0]
     assert not info.inexact
     assert_pairs(name, lam, y, info, TOL64, f"{np.dtype(fdtype).name} factor")
 
@@ -308,7 +198,7 @@ def test_f32_matrix_with_an_f32_factor(monkeypatch):
 @pytest.mark.parametrize("name", ["g11-leaf8", "random"])
 def test_calls_repeat_and_v0_restates_the_seed(monkeypatch, name):
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     A = matrix(name, F64)
     with cholesky_nd(A, factor_dtype=F32) as f:
         want = parts(*f.eigsh(A, NEV, block=BLOCK, ncv=NCV[name], seed=3))
@@ -324,8 +214,8 @@ def test_calls_repeat_and_v0_restates_the_seed(monkeypatch, name):
 def test_the_upper_triangle_is_ignored(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    r, c = _coords(name)
-    v = _system(name)[3]
+    r, c = coords(name)
+    v = system(name)[3]
     junk = np.where(c > r, 1e6 * (1.0 + np.arange(v.size)), v)
     with cholesky_nd(matrix(name, F64), factor_dtype=F32) as f:
         want = parts(*f.eigsh(matrix(name, F64), NEV, block=BLOCK, ncv=NCV[name]))
@@ -341,7 +231,7 @@ def test_device_call_and_switches_have_the_default_host_calls_bits(monkeypatch, 
 
     name = "g40-leaf256"
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     want = parts(*_default_run(name, F32))  # made (or to be made now) without the switches
     for key, val in env.items():
         monkeypatch.setenv(key, val)
@@ -448,11 +338,11 @@ def test_edge_cases(monkeypatch):
         with pytest.raises(TypeError):
             f.eigsh(A, NEV, v0=Dense.from_columns([np.ones(n, dtype=F32)] * BLOCK))
         with pytest.raises(TypeError):
-            f.eigsh(matrix(name, np.int32, np.ones(_system(name)[3].size)), NEV)
+            f.eigsh(matrix(name, np.int32, np.ones(system(name)[3].size)), NEV)
         with pytest.raises(ValueError, match="ncv"):
             f.eigsh(A, NEV, ncv=n + 4)
-        bad = _system(name)[3].copy()
-        r, c = _coords(name)
+        bad = system(name)[3].copy()
+        r, c = coords(name)
         e = int(np.nonzero((r == n // 2) & (c == n // 2))[0][0])
         bad[e] = -bad[e]
         with pytest.raises(_lib.BsmError):

@@ -2,7 +2,7 @@
 Lanczos on a kept nd factor (NdFactor.eigsh(m=...), device.nd_factor_eigsh(m=...),
 bsm_nd_factor_eigsh_gen).
 
-The systems restate test_gpu_nd_eig.py's small generators: A is the 5-point
+The Poisson systems are nd_support.py's: A is the 5-point
 Poisson matrix of a g x g grid with the consistent mass matrix kron(M1, M1), M1
 = tridiag(1/6, 4/6, 1/6) (a 9-point pattern on a 5-point A): one-pivot fronts
 (g9-leaf1), several levels (g11-leaf8), multi-tile fronts (g40-leaf256); and an
@@ -33,30 +33,20 @@ import functools
 import numpy as np
 import pytest
 
+import nd_support
 from basic_sparse_matrix_amd import Csr, Dense, EigInfo, MatErr, _lib, cholesky_nd
+from nd_support import _scale, assert_same, cols_of, csr_arrays, same_bits, start_block
 
 pytestmark = pytest.mark.gpu
 
-POISSON = {"g9-leaf1": (9, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["random"]
+POISSON = ["g9-leaf1", "g11-leaf8", "g40-leaf256"]
+SYSTEMS = POISSON + ["random"]
 NCV = {"g9-leaf1": 80, "g11-leaf8": 60, "g40-leaf256": 60, "random": 160}
 F32, F64 = np.float32, np.float64
 NEV, BLOCK = 6, 4
 TOL64, TOL32 = 2.0 ** -26, 2.0 ** -12
 U = 2.0 ** -53
 G11 = "g11-leaf8"
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
 
 
 def _random_spd(seed, density, shift):
@@ -74,13 +64,10 @@ def _random_spd(seed, density, shift):
 
 @functools.lru_cache(maxsize=None)
 def _system(name):
-    """(n, rp, ci, v as f64, leaf or None) of A, built once."""
-    from oracle import pyoracle as orc
-
+    """(n, rp, ci, v as f64, leaf or None) of A, built once. `random` is this file's own: its diagonal is the row sum
+    plus (1 + r) where nd_support's is (the row sum plus 1) plus r, so the two matrices differ in the last bit."""
     if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
+        return nd_support.system(name)
     a = _random_spd(7, 0.02, lambda rng, n: 1.0 + rng.random(n))  # an irregular tree
     rp, ci, v = csr_arrays(a)
     return a.shape[0], rp, ci, v, None
@@ -99,7 +86,7 @@ def _mass(name, kind="consistent"):
     if kind == "minus":
         return csr_arrays(-np.eye(n))
     if name in POISSON:
-        g = POISSON[name][0]
+        g = nd_support.POISSON[name][0]
         m1 = (np.diag(np.full(g, 4.0)) + np.diag(np.ones(g - 1), 1) + np.diag(np.ones(g - 1), -1)) / 6.0
         return csr_arrays(np.kron(m1, m1))
     return csr_arrays(_random_spd(11, 0.01, lambda rng, n: rng.uniform(0.5, 2.0, n)))
@@ -149,20 +136,10 @@ def mass(name, dtype, kind="consistent"):
     return Csr.from_csr_arrays((n, n), rp, ci, np.asarray(v).astype(dtype))
 
 
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
-
-
 def parts(lam, y, info):
     return [lam] + (cols_of(y) if y is not None else []) + [info.resid, info.converged,
                                                            np.array([info.steps, info.ncv_used, info.exhausted,
                                                                      info.inexact])]
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
 
 
 def assert_pairs(name, kind, lam, y, info, tol, what, dtype=F64, count=NEV):
@@ -206,41 +183,7 @@ def c_info(f, A, M, nev, block, ncv, tol=0.0, seed=0):
     return rc, lam, resid, info
 
 
-# ---- the start block, restated: bsm_hash(seed, row, column, 6) mapped to [-1, 1) ------------
-
-M64 = (1 << 64) - 1
-
-
-def _mix64(z):
-    z = (z + 0x9E3779B97F4A7C15) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-@functools.lru_cache(maxsize=None)
-def _start_block(n, block, seed):
-    out = np.zeros((n, block))
-    h0 = _mix64(seed ^ ((6 * 0xD1B54A32D192ED03) & M64))
-    for r in range(n):
-        hr = _mix64(h0 ^ r)
-        for c in range(block):
-            h = _mix64(hr ^ ((c * 0x9E3779B97F4A7C15) & M64))
-            out[r, c] = 2.0 * ((0.5 + (h >> 11) * 2.0 ** -53) - 1.0)
-    out.setflags(write=False)
-    return out
-
-
-def start_block(n, block, seed=0, dtype=F64):
-    return _start_block(n, block, seed).astype(dtype)
-
-
 # ---- the loop in the S_M inner product, emulated: np.linalg.cholesky in the factor's dtype as the factor ----
-
-
-def _scale(v):
-    m = np.abs(v).max()
-    return 2.0 ** np.floor(np.log2(m)) if m > 0 and np.isfinite(m) else 1.0
 
 
 @functools.lru_cache(maxsize=None)

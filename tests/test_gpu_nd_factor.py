@@ -20,39 +20,19 @@ import gc
 import numpy as np
 import pytest
 
+import nd_support
 from basic_sparse_matrix_amd import (Csr, Dense, Panic, backward_substitution, cholesky_nd, forward_substitution,
                                      solve)
+from nd_support import csr_arrays, dense_of, matrix, rel_err, rhs_cols, same_bits, system
 
 pytestmark = pytest.mark.gpu
 
 TOL = {np.float64: 1e-10, np.float32: 2e-3}
 
-# (g, BSM_ND_LEAF) of orc.poisson2d(g)
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g11-onefront": (11, "100000"), "g40-leaf64": (40, "64"),
-           "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+POISSON = ["g5-leaf1", "g11-leaf8", "g11-onefront", "g40-leaf64", "g40-leaf256"]
+SYSTEMS = POISSON + ["blocks", "random"]
 CASES = [(s, np.float64) for s in SYSTEMS] + [(s, np.float32) for s in POISSON]
 CASE_IDS = [f"{s}-{np.dtype(d).name}" for s, d in CASES]
-
-
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def dense_of(rp, ci, v, n):
-    a = np.zeros((n, n), dtype=np.float64)
-    rows = np.repeat(np.arange(n), np.diff(np.asarray(rp).astype(np.int64)))
-    a[rows, np.asarray(ci).astype(np.int64)] = np.asarray(v, dtype=np.float64)
-    return a
 
 
 def dense_of_csr(m):
@@ -60,60 +40,19 @@ def dense_of_csr(m):
 
 
 @functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, band oracle usable, leaf or None), built once."""
+def _reference(name):
+    """The oracle's f64 solution of the three right-hand columns, once per system: the band restatement, and the
+    literal one for the random matrix."""
     from oracle import pyoracle as orc
 
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, v, True, leaf
-    if name == "blocks":  # test_nd_disconnected_blocks' matrix: fronts with np == 0
-        import scipy.sparse as sp
-
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return (M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), True,
-                None)
-    rng = np.random.default_rng(7)  # test_nd_random_spd_vs_oracle's matrix: an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, False, None
-
-
-@functools.lru_cache(maxsize=None)
-def _rhs_and_reference(name):
-    """Three f64 right-hand columns and the oracle's f64 solution, once per system."""
-    from oracle import pyoracle as orc
-
-    n, rp, ci, v, band, _ = _system(name)
-    b = orc.gen_x_cols(2001, n, 3)
-    ex = orc.solve(n, rp, ci, v, b, band=band)
-    return b, ex
+    n, rp, ci, v, _ = system(name)
+    return orc.solve(n, rp, ci, v, rhs_cols(name), band=name != "random")
 
 
 def setup(monkeypatch, name, dtype):
-    n, rp, ci, v, _, leaf = _system(name)
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-    b64, ex = _rhs_and_reference(name)
-    A = Csr.from_csr_arrays((n, n), rp, ci, v.astype(dtype))
-    b = [c.astype(dtype) for c in b64]
-    return n, A, b, ex
-
-
-def same_bits(x, y):
-    return np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8))
+    nd_support.setup(monkeypatch, name)
+    b = [c.astype(dtype) for c in rhs_cols(name)]
+    return system(name)[0], matrix(name, dtype), b, _reference(name)
 
 
 @pytest.mark.parametrize("name,dtype", CASES, ids=CASE_IDS)
@@ -150,7 +89,7 @@ def test_reuse_survives_other_solves_free_and_cache_clear(monkeypatch):
     from oracle import pyoracle as orc
 
     n, A, _, _ = setup(monkeypatch, "g40-leaf64", np.float64)
-    _, rp, ci, v, _, _ = _system("g40-leaf64")
+    _, rp, ci, v, _ = system("g40-leaf64")
     f = cholesky_nd(A)
     last = None
     for seed in (2101, 2102, 2103):

@@ -20,16 +20,17 @@ import threading
 import numpy as np
 import pytest
 
+import nd_support
 from basic_sparse_matrix_amd import (Csr, Dense, _lib, backward_substitution, cholesky_nd, forward_substitution)
+from nd_support import (assert_same, cols_of, coords, csr_arrays, csr_parts, dense_of, rel_err, rhs_cols, same_bits,
+                        system)
 
 pytestmark = pytest.mark.gpu
 
 TOL = {np.float64: 1e-10, np.float32: 2e-3}
 
-# (g, BSM_ND_LEAF) of orc.poisson2d(g)
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g11-onefront": (11, "100000"), "g40-leaf64": (40, "64"),
-           "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+POISSON = ["g5-leaf1", "g11-leaf8", "g11-onefront", "g40-leaf64", "g40-leaf256"]
+SYSTEMS = POISSON + ["blocks", "random"]
 CASES = [(s, np.float64) for s in SYSTEMS] + [(s, np.float32) for s in POISSON]
 CASE_IDS = [f"{s}-{np.dtype(d).name}" for s, d in CASES]
 # a subset for the checks that repeat one property under other switches
@@ -37,68 +38,11 @@ FEW = [("g5-leaf1", np.float32), ("g11-onefront", np.float64), ("g40-leaf256", n
 FEW_IDS = [f"{s}-{np.dtype(d).name}" for s, d in FEW]
 
 
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def dense_of(rp, ci, v, n):
-    a = np.zeros((n, n), dtype=np.float64)
-    rows = np.repeat(np.arange(n), np.diff(np.asarray(rp).astype(np.int64)))
-    a[rows, np.asarray(ci).astype(np.int64)] = np.asarray(v, dtype=np.float64)
-    return a
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, leaf or None), built once."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
-    if name == "blocks":  # fronts with np == 0
-        import scipy.sparse as sp
-
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    rng = np.random.default_rng(7)  # an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, None
-
-
 @functools.lru_cache(maxsize=None)
 def _values(name):
     """The three value sets of a pattern, f64: A's, A2 = D A D's, and A's with one diagonal entry negated."""
-    n, rp, ci, v, _ = _system(name)
-    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
-    cols = ci.astype(np.int64)
+    n, _, _, v, _ = system(name)
+    rows, cols = coords(name)
     d = 1.0 + np.random.default_rng(11).random(n)
     v2 = d[rows] * v * d[cols]
     bad = v.copy()
@@ -107,33 +51,14 @@ def _values(name):
     return v, v2, bad
 
 
-@functools.lru_cache(maxsize=None)
-def _rhs(name):
-    from oracle import pyoracle as orc
-
-    return orc.gen_x_cols(2001, _system(name)[0], 3)
-
-
 def setup(monkeypatch, name, dtype):
-    n, rp, ci, _, leaf = _system(name)
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-    b = [c.astype(dtype) for c in _rhs(name)]
-    return n, b
+    nd_support.setup(monkeypatch, name)
+    return system(name)[0], [c.astype(dtype) for c in rhs_cols(name)]
 
 
 def matrix(name, dtype, which=0):
     """A fresh Csr (a fresh device handle) of the pattern with value set `which`."""
-    n, rp, ci, _, _ = _system(name)
-    return Csr.from_csr_arrays((n, n), rp, ci, _values(name)[which].astype(dtype))
-
-
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
-
-
-def csr_parts(m):
-    return [np.asarray(m.row_index).copy(), np.asarray(m.col_index).copy(), np.asarray(m.v).copy()]
+    return nd_support.matrix(name, dtype, _values(name)[which])
 
 
 def snapshot(f, b):
@@ -143,12 +68,6 @@ def snapshot(f, b):
         out += cols_of(f.solve(Dense.from_columns(b[:k])))
     out += csr_parts(f.l()) + csr_parts(f.l_star()) + [f.perm]
     return out
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
 
 
 def invalid(match):
@@ -212,7 +131,7 @@ def test_refactor_after_cache_clear_and_free_of_a(monkeypatch):
     assert _lib.nd_cache_info()["entries"] == 0
     f.refactor(matrix(name, dtype, 1))
     assert_same(snapshot(f, b), want)
-    n, rp, ci, _, _ = _system(name)
+    n, rp, ci, _, _ = system(name)
     moved = ci.copy()
     moved[1] += 1  # row 0 of the grid: columns 0, 1, g -> 0, 2, g
     with invalid("col differs"):
@@ -229,7 +148,7 @@ def test_refactor_with_the_caches_off(monkeypatch, switch):
     monkeypatch.setenv(switch, "0")
     name, dtype = "g11-leaf8", np.float64
     n, b = setup(monkeypatch, name, dtype)
-    _, rp, ci, _, _ = _system(name)
+    _, rp, ci, _, _ = system(name)
     A = matrix(name, dtype)
     with cholesky_nd(A) as f, cholesky_nd(A) as second, cholesky_nd(matrix(name, dtype, 1)) as fresh:
         base, want = snapshot(f, b), snapshot(fresh, b)
@@ -264,7 +183,7 @@ def test_refactor_rejections_leave_the_factor_untouched(monkeypatch):
 
     name, dtype = "g11-leaf8", np.float64
     n, b = setup(monkeypatch, name, dtype)
-    _, rp, ci, v, _ = _system(name)
+    _, rp, ci, v, _ = system(name)
     with cholesky_nd(matrix(name, dtype)) as f:
         base = snapshot(f, b)
         with invalid("dtype differs"):
@@ -300,7 +219,7 @@ def test_refactor_not_positive_definite_empties_the_factor(monkeypatch, name, dt
     from basic_sparse_matrix_amd import device
 
     n, b = setup(monkeypatch, name, dtype)
-    _, rp, ci, _, _ = _system(name)
+    _, rp, ci, _, _ = system(name)
     bad = _values(name)[2]
     with pytest.raises(np.linalg.LinAlgError):
         np.linalg.cholesky(dense_of(rp, ci, bad, n))
@@ -332,7 +251,7 @@ def test_refactor_not_positive_definite_empties_the_factor(monkeypatch, name, dt
 @pytest.mark.parametrize("name,dtype", CASES, ids=CASE_IDS)
 def test_logdet(monkeypatch, name, dtype):
     n, _ = setup(monkeypatch, name, dtype)
-    _, rp, ci, _, _ = _system(name)
+    _, rp, ci, _, _ = system(name)
     v, v2, _ = (x.astype(dtype) for x in _values(name))
     sign, ref = np.linalg.slogdet(dense_of(rp, ci, v, n))
     assert sign == 1.0

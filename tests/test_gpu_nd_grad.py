@@ -2,8 +2,9 @@
 (the numeric factor again from device values), inv_pattern (S^-1 on the kept
 pattern, on the device), and autograd.nd_solve / nd_logdet with their guards.
 
-The systems, second values (A2 = D A D), the not-positive-definite variant and
-the helpers are tests/test_gpu_nd_factor_ops.py's, with its tolerances
+The systems are nd_support.py's; the second values (A2 = D A D), the
+not-positive-definite variant and snapshot() are
+tests/test_gpu_nd_factor_ops.py's, with its tolerances
 TOL = {f64: 1e-10, f32: 2e-3}. The gradients are compared with the dense f64
 formulas, evaluated with numpy on the CPU from the dense S (the stored entries
 with col <= row, mirrored), G the upstream gradient and Λ = S^-1 G:
@@ -21,8 +22,9 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, _lib, cholesky_nd
-from test_gpu_nd_factor_ops import (TOL, _system, _values, assert_same, dense_of, invalid, matrix, rel_err, same_bits,
-                                    setup, snapshot)
+from nd_support import assert_same, coords, rel_err, same_bits, sym_dense, system
+# the value sets (A2 = D A D, the not-positive-definite one) and what a factor answers are that feature's
+from test_gpu_nd_factor_ops import TOL, _values, invalid, matrix, setup, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -44,8 +46,7 @@ def everything(f, b):
 
 def pattern(name):
     """(n, rows, cols) of the stored entries, in storage order."""
-    n, rp, ci, _, _ = _system(name)
-    return n, np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)
+    return (system(name)[0], *coords(name))
 
 
 # ---- refactor_values --------------------------------------------------------
@@ -196,9 +197,7 @@ def test_inv_pattern_has_the_bits_of_inv_on(monkeypatch, name, dtype):
 
 def sym_of(name, dtype, which=0):
     """The dense S (f64) of the value set as the dtype stores it: col <= row, mirrored."""
-    n, rp, ci, _, _ = _system(name)
-    a = np.tril(dense_of(rp, ci, _values(name)[which].astype(dtype), n))
-    return a + np.tril(a, -1).T
+    return sym_dense(name, _values(name)[which].astype(dtype))
 
 
 @functools.lru_cache(maxsize=None)
@@ -207,7 +206,7 @@ def inverse(name, dtype):
 
 
 def rhs(name, k, dtype, seed):
-    n = _system(name)[0]
+    n = system(name)[0]
     r = np.random.default_rng(seed).standard_normal((n, k) if k > 1 else (n,))
     return r.astype(dtype)
 

@@ -6,11 +6,12 @@ in refactor's order. So the contract is EQUALITY with a fresh cholesky_nd of
 the new matrix (same_bits / np.array_equal on l(), solve, logdet, inv_diag);
 nothing here has a tolerance but eigsh's own residual test.
 
-The systems, their BSM_ND_LEAF and the places (through the permutation from
-nd_analyse) are test_gpu_nd_sparse_solve.py's, imported from it. A changed
-diagonal entry grows by a multiple of 1/4 and a changed edge shrinks to 3/4 of
-its value (both triangles, though the upper one is never read), so every new
-matrix stays diagonally dominant, hence SPD, and f32 holds its values."""
+The systems and their BSM_ND_LEAF are nd_support.dense_system's; the places
+(through the permutation from nd_analyse) are test_gpu_nd_sparse_solve.py's.
+A changed diagonal entry grows by a multiple of 1/4 and a changed edge shrinks
+to 3/4 of its value (both triangles, though the upper one is never read), so
+every new matrix stays diagonally dominant, hence SPD, and f32 holds its
+values."""
 
 import functools
 import json
@@ -20,10 +21,11 @@ import sys
 
 import numpy as np
 import pytest
-import test_gpu_nd_sparse_solve as base
-from test_gpu_nd_sparse_solve import DTYPES, SYSTEMS, _places, _system, _tree, b_csr, matrix, reach, same_bits, setup
 
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, MatErrKind, _lib, cholesky_nd
+from nd_support import assert_same, dense_matrix, dense_setup, dense_system
+# the places through nd_analyse's tree, and the cases, are the sparse solve's
+from test_gpu_nd_sparse_solve import DTYPES, SYSTEMS, _places, _tree, arr, b_csr, path, reach
 
 gpu = pytest.mark.gpu
 
@@ -36,7 +38,7 @@ FEW_IDS = [f"{s}-{np.dtype(d[0]).name}-factor-{np.dtype(d[1]).name}" for s, d in
 
 def _leaf_edge(name, leaf):
     """A stored off-diagonal (i, j) with both ends among `leaf`'s own vertices, or None."""
-    s, t = _system(name)[1], _tree(name)
+    s, t = dense_system(name)[1], _tree(name)
     vs = [int(v) for v in t["perm"][t["start"][leaf]:t["end"][leaf]]]
     for i in vs:
         for j in vs:
@@ -48,7 +50,7 @@ def _leaf_edge(name, leaf):
 @functools.lru_cache(maxsize=None)
 def groups(name):
     """name -> the list of (i, j) positions (A's order) of each case the module's tests walk."""
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     t, p = _tree(name), _places(name)
     pinv = t["pinv"]
     out = {"leaf-diagonal": [(p["a"], p["a"])], "root": [(p["last"], p["last"])]}
@@ -98,7 +100,7 @@ def rc(pairs):
 
 
 def rhs(name, dtype):
-    n = _system(name)[0]
+    n = dense_system(name)[0]
     b = (np.arange(n) % 7 - 3.0) / 4.0
     return np.ascontiguousarray(b.astype(dtype))
 
@@ -111,13 +113,8 @@ def bits(f, name):
             np.asarray(f.inv_diag())]
 
 
-def assert_same(got, want, what=""):
-    for q, (x, y) in enumerate(zip(got, want)):
-        assert same_bits(x, y), f"{what}: piece {q} differs"
-
-
 def fresh_bits(s, name, src, fdt):
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as g:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as g:
         return bits(g, name)
 
 
@@ -126,13 +123,13 @@ def fresh_bits(s, name, src, fdt):
 
 def test_the_groups_start_where_they_should():
     t, p, g = _tree("g11-leaf8"), _places("g11-leaf8"), groups("g11-leaf8")
-    assert reach("g11-leaf8", start_vertices("g11-leaf8", g["leaf-edge"])) == set(base.path("g11-leaf8", p["leaf_a"]))
+    assert reach("g11-leaf8", start_vertices("g11-leaf8", g["leaf-edge"])) == set(path("g11-leaf8", p["leaf_a"]))
     assert t["level"][t["owner"][t["pinv"][start_vertices("g11-leaf8", g["separator"])[0]]]] > 0
     assert len(reach("g11-leaf8", start_vertices("g11-leaf8", g["every-entry"]))) == len(t["start"])
     assert "second-tile" in groups("g40-leaf256")
     tb = _tree("blocks")
     assert len(reach("blocks", start_vertices("blocks", groups("blocks")["seeded-17"]))) < len(tb["start"])
-    n, s, _, _ = _system("g40-leaf256")
+    n, s, _, _ = dense_system("g40-leaf256")
     s2 = changed(s, groups("g40-leaf256")["every-entry"])
     assert (np.abs(s2).sum(axis=1) - 2 * np.diag(s2) <= 0).all()  # still diagonally dominant
 
@@ -143,37 +140,37 @@ def test_the_groups_start_where_they_should():
 @gpu
 @pytest.mark.parametrize("name,dt", CASES, ids=CASE_IDS)
 def test_partial_equals_a_fresh_factor(monkeypatch, name, dt):
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dt
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     t = _tree(name)
     base0 = fresh_bits(s, name, src, fdt)
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
         for gname, pairs in groups(name).items():
             s2 = changed(s, pairs)
             rows, cols = rc(pairs)
-            info = f.refactor_partial(matrix(s2, src), rows, cols)
+            info = f.refactor_partial(dense_matrix(s2, src), rows, cols)
             want = len(reach(name, start_vertices(name, pairs)))
             assert (info.fronts, info.total_fronts, info.changed) == (want, len(t["start"]), len(pairs)), gname
             if gname == "every-entry":
                 assert info.fronts == info.total_fronts
             assert_same(bits(f, name), fresh_bits(s2, name, src, fdt), gname)
             # and back: the same places named, the first matrix's values
-            info = f.refactor_partial(matrix(s, src), rows, cols)
+            info = f.refactor_partial(dense_matrix(s, src), rows, cols)
             assert info.fronts == want
             assert_same(bits(f, name), base0, gname + " (back)")
 
 
 @gpu
 def test_blocks_other_component_is_not_counted(monkeypatch):
-    setup(monkeypatch, "blocks")
-    n, s, _, _ = _system("blocks")
+    dense_setup(monkeypatch, "blocks")
+    n, s, _, _ = dense_system("blocks")
     t = _tree("blocks")
     pairs = groups("blocks")["seeded-17"]
     first = {int(x) for x in range(len(t["start"])) if t["end"][x] > t["start"][x]
              and t["perm"][t["start"][x]] < 144}  # fronts with a vertex of the first grid
-    with cholesky_nd(matrix(s, np.float64)) as f:
-        info = f.refactor_partial(matrix(changed(s, pairs), np.float64), *rc(pairs))
+    with cholesky_nd(dense_matrix(s, np.float64)) as f:
+        info = f.refactor_partial(dense_matrix(changed(s, pairs), np.float64), *rc(pairs))
     active = reach("blocks", start_vertices("blocks", pairs))
     assert info.fronts == len(active) and not (active & first) and info.fronts < info.total_fronts
 
@@ -185,16 +182,16 @@ def test_blocks_other_component_is_not_counted(monkeypatch):
 @pytest.mark.parametrize("dt", DTYPES, ids=[f"{np.dtype(a).name}-factor-{np.dtype(b).name}" for a, b in DTYPES])
 def test_only_the_named_paths_are_rerun(monkeypatch, dt):
     name = "g11-leaf8"
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dt
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     p = _places(name)
     ea, eb = (p["a"], p["a"]), (p["b"], p["b"])
     s2, s3 = changed(s, [ea, eb]), changed(s, [ea])
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
-        f.refactor_partial(matrix(s2, src), [ea[0]], [ea[1]])  # b's entry changed too, but is not named
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
+        f.refactor_partial(dense_matrix(s2, src), [ea[0]], [ea[1]])  # b's entry changed too, but is not named
         assert_same(bits(f, name), fresh_bits(s3, name, src, fdt), "a alone")
-        f.refactor_partial(matrix(s2, src), [eb[0]], [eb[1]])
+        f.refactor_partial(dense_matrix(s2, src), [eb[0]], [eb[1]])
         assert_same(bits(f, name), fresh_bits(s2, name, src, fdt), "then b")
 
 
@@ -204,17 +201,17 @@ def test_only_the_named_paths_are_rerun(monkeypatch, dt):
 @gpu
 @pytest.mark.parametrize("name,dt", CASES, ids=CASE_IDS)
 def test_since_finds_the_places(monkeypatch, name, dt):
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dt
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     t = _tree(name)
-    a0 = matrix(s, src)
+    a0 = dense_matrix(s, src)
     with cholesky_nd(a0, factor_dtype=fdt) as f:
         base0 = bits(f, name)
         for gname in ("two-leaves", "seeded-17", "every-entry"):
             pairs = groups(name)[gname]
             s2 = changed(s, pairs)
-            a2 = matrix(s2, src)
+            a2 = dense_matrix(s2, src)
             info = f.refactor_partial(a2, since=a0)
             assert info.changed == int((np.tril(s2) != np.tril(s)).sum()) == len(set(pairs)), gname
             assert info.fronts == len(reach(name, start_vertices(name, pairs))) and info.total_fronts == len(t["start"])
@@ -225,7 +222,7 @@ def test_since_finds_the_places(monkeypatch, name, dt):
         i, j = next((i, j) for i, j in groups(name)["every-entry"] if i > j)
         up = np.array(s)
         up[j, i] = 0.5 * s[i, j]
-        for other in (matrix(up, src), a0):
+        for other in (dense_matrix(up, src), a0):
             info = f.refactor_partial(other, since=a0)
             assert (info.fronts, info.changed) == (0, 0)
             assert_same(bits(f, name), base0, "no differing entry")
@@ -237,34 +234,34 @@ def test_since_finds_the_places(monkeypatch, name, dt):
 @gpu
 @pytest.mark.parametrize("name,dt", FEW, ids=FEW_IDS)
 def test_sequences(monkeypatch, name, dt):
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dt
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     g = groups(name)
     s1 = changed(s, g["two-leaves"])
     s2 = changed(s1, g["separator"] + g["root"])
     s3 = changed(changed(s, g["every-entry"]), g["leaf-diagonal"])
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
-        f.refactor_partial(matrix(s1, src), *rc(g["two-leaves"]))
-        f.refactor_partial(matrix(s2, src), *rc(g["separator"] + g["root"]))  # partial after partial
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
+        f.refactor_partial(dense_matrix(s1, src), *rc(g["two-leaves"]))
+        f.refactor_partial(dense_matrix(s2, src), *rc(g["separator"] + g["root"]))  # partial after partial
         want = fresh_bits(s2, name, src, fdt)
         assert_same(bits(f, name), want, "partial after partial")
-        f.refactor_partial(matrix(s2, src), *rc(g["separator"] + g["root"]))  # a repeat
+        f.refactor_partial(dense_matrix(s2, src), *rc(g["separator"] + g["root"]))  # a repeat
         assert_same(bits(f, name), want, "repeat")
-        f.refactor(matrix(changed(s, g["every-entry"]), src))
-        f.refactor_partial(matrix(s3, src), *rc(g["leaf-diagonal"]))  # partial after refactor
+        f.refactor(dense_matrix(changed(s, g["every-entry"]), src))
+        f.refactor_partial(dense_matrix(s3, src), *rc(g["leaf-diagonal"]))  # partial after refactor
         assert_same(bits(f, name), fresh_bits(s3, name, src, fdt), "partial after refactor")
 
 
 @gpu
 def test_the_other_calls_see_the_new_factor(monkeypatch):
     name = "g11-leaf8"
-    setup(monkeypatch, name)
-    n, s, _, _ = _system(name)
+    dense_setup(monkeypatch, name)
+    n, s, _, _ = dense_system(name)
     g = groups(name)
     pairs = g["two-leaves"] + g["separator"]
     s2 = changed(s, pairs)
-    a2 = matrix(s2, np.float64)
+    a2 = dense_matrix(s2, np.float64)
     bs = np.zeros((n, 2))
     bs[_places(name)["a"], 0] = 1.0
     bs[_places(name)["sep"], 1] = -0.5
@@ -275,11 +272,11 @@ def test_the_other_calls_see_the_new_factor(monkeypatch):
     def calls(f):
         x = f.solve_sparse(b_csr(bs, np.float64), rows)
         xr, ri = f.solve_refined(a2, bd)
-        out = [base.arr(x), np.asarray(f.inv_entries(er, ec)), np.asarray(xr.get_col(0)), ri.iters, ri.berr]
+        out = [arr(x), np.asarray(f.inv_entries(er, ec)), np.asarray(xr.get_col(0)), ri.iters, ri.berr]
         lam, _, ei = f.eigsh(a2, 2)
         return out, lam, ei
 
-    with cholesky_nd(matrix(s, np.float64)) as f, cholesky_nd(a2) as fresh:
+    with cholesky_nd(dense_matrix(s, np.float64)) as f, cholesky_nd(a2) as fresh:
         f.refactor_partial(a2, *rc(pairs))
         got, lam, ei = calls(f)
         want, lam_w, ei_w = calls(fresh)
@@ -296,19 +293,19 @@ def test_the_other_calls_see_the_new_factor(monkeypatch):
 @pytest.mark.parametrize("dt", DTYPES, ids=[f"{np.dtype(a).name}-factor-{np.dtype(b).name}" for a, b in DTYPES])
 def test_refusals_leave_the_factor(monkeypatch, dt):
     name = "g11-leaf8"
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dt
     other = np.float32 if src == np.float64 else np.float64
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     g, p = groups(name), _places(name)
     pairs = g["two-leaves"]
     s2 = changed(s, pairs)
-    a2 = matrix(s2, src)
+    a2 = dense_matrix(s2, src)
 
     def l_bits(f):
         return [np.asarray(x) for x in f.l()._csr_arrays()]
 
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
         before = l_bits(f)
         far = next((i, j) for i in range(n) for j in range(i) if s[i, j] == 0)
         with pytest.raises(_lib.BsmError, match="not stored") as e:  # a pair that is not stored
@@ -322,33 +319,34 @@ def test_refusals_leave_the_factor(monkeypatch, dt):
         sp = np.array(s2)
         sp[far[0], far[1]] = sp[far[1], far[0]] = -0.25
         with pytest.raises(_lib.BsmError, match="nd factor refactor: nnz differs") as e:  # another pattern
-            f.refactor_partial(matrix(sp, src), *rc(pairs))
+            f.refactor_partial(dense_matrix(sp, src), *rc(pairs))
         assert e.value.code == _lib.BSM_ERR_INVALID
         sq = np.array(sp)  # the same nnz, another col
         drop = next((i, j) for i, j in g["every-entry"] if i != j and (i, j) not in pairs)
         sq[drop[0], drop[1]] = sq[drop[1], drop[0]] = 0.0
         with pytest.raises(_lib.BsmError, match="nd factor refactor: (row_ptr|col) differs") as e:
-            f.refactor_partial(matrix(sq, src), *rc(pairs))
+            f.refactor_partial(dense_matrix(sq, src), *rc(pairs))
         assert e.value.code == _lib.BSM_ERR_INVALID
         with pytest.raises(_lib.BsmError, match="nd factor refactor: dtype differs") as e:  # a wrong dtype
-            f.refactor_partial(matrix(s2, other), *rc(pairs))
+            f.refactor_partial(dense_matrix(s2, other), *rc(pairs))
         assert e.value.code == _lib.BSM_ERR_INVALID
         with pytest.raises(_lib.BsmError, match="nd factor refactor: dtype differs"):
-            f.refactor_partial(matrix(s2, other), since=matrix(s, other))
+            f.refactor_partial(dense_matrix(s2, other), since=dense_matrix(s, other))
         with pytest.raises(TypeError):  # the two matrices of a since= call differ in dtype: refused on the host
-            f.refactor_partial(matrix(s2, src), since=matrix(s, other))
+            f.refactor_partial(dense_matrix(s2, src), since=dense_matrix(s, other))
         assert_same(l_bits(f), before)
         # after update: refused until a refactor
         w = np.zeros((n, 1))
         w[p["a"], 0] = 0.5
         f.update(b_csr(w, src))
         after_update = l_bits(f)
-        for kw in ({"rows": rc(pairs)[0], "cols": rc(pairs)[1]}, {"since": matrix(s, src)}, {"rows": [], "cols": []}):
+        for kw in ({"rows": rc(pairs)[0], "cols": rc(pairs)[1]}, {"since": dense_matrix(s, src)},
+                   {"rows": [], "cols": []}):
             with pytest.raises(_lib.BsmError, match="refactor first") as e:
                 f.refactor_partial(a2, **kw)
             assert e.value.code == _lib.BSM_ERR_UNSUPPORTED
         assert_same(l_bits(f), after_update)
-        f.refactor(matrix(s, src))
+        f.refactor(dense_matrix(s, src))
         assert_same(l_bits(f), before)
         info = f.refactor_partial(a2, *rc(pairs))
         assert info.fronts == len(reach(name, start_vertices(name, pairs)))
@@ -365,25 +363,25 @@ def test_refusals_leave_the_factor(monkeypatch, dt):
 @gpu
 def test_not_positive_definite(monkeypatch):
     name = "g11-leaf8"
-    setup(monkeypatch, name)
-    n, s, _, _ = _system(name)
+    dense_setup(monkeypatch, name)
+    n, s, _, _ = dense_system(name)
     v = _places(name)["a"]
     bad = np.array(s)
     bad[v, v] = -1.0
-    with cholesky_nd(matrix(s, np.float64)) as f:
+    with cholesky_nd(dense_matrix(s, np.float64)) as f:
         good = bits(f, name)
         with pytest.raises(_lib.BsmError, match="cholesky: matrix is not positive definite") as e:
-            f.refactor_partial(matrix(bad, np.float64), [v], [v])
+            f.refactor_partial(dense_matrix(bad, np.float64), [v], [v])
         assert e.value.code == _lib.BSM_ERR_UNSUPPORTED
         with pytest.raises(_lib.BsmError, match="holds no values") as e:
             f.solve(Dense.from_columns([rhs(name, np.float64)]))
         assert e.value.code == _lib.BSM_ERR_INVALID
-        f.refactor(matrix(s, np.float64))
+        f.refactor(dense_matrix(s, np.float64))
         assert_same(bits(f, name), good, "restored")
         # a handle without values has no update blocks to pull: a partial call factors every front
         with pytest.raises(_lib.BsmError, match="not positive definite"):
-            f.refactor_partial(matrix(bad, np.float64), since=matrix(s, np.float64))
-        info = f.refactor_partial(matrix(s, np.float64), [v], [v])
+            f.refactor_partial(dense_matrix(bad, np.float64), since=dense_matrix(s, np.float64))
+        info = f.refactor_partial(dense_matrix(s, np.float64), [v], [v])
         assert info.fronts == info.total_fronts
         assert_same(bits(f, name), good, "restored by a partial call")
 
@@ -395,7 +393,7 @@ def test_not_positive_definite(monkeypatch):
 @pytest.mark.parametrize("switch", ["BSM_ND_PLAIN=1", "BSM_ND_LAG=0", "BSM_ND_POISON=1"])
 def test_pipeline_switches(switch):
     key, val = switch.split("=")
-    env = dict(os.environ, **{key: val, "BSM_ND_LEAF": _system("g11-leaf8")[3]})
+    env = dict(os.environ, **{key: val, "BSM_ND_LEAF": dense_system("g11-leaf8")[3]})
     r = subprocess.run([sys.executable, os.path.join(HERE, "nd_partial_worker.py"), "g11-leaf8"], capture_output=True,
                        text=True, timeout=240, env=env, cwd=HERE)
     assert r.returncode == 0, r.stdout + r.stderr

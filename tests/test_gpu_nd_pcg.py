@@ -1,7 +1,7 @@
 """GPU tests of preconditioned conjugate gradients on a kept nd factor
 (NdFactor.solve_pcg, device.nd_factor_solve_pcg, bsm_nd_factor_solve_pcg).
 
-The systems restate test_gpu_nd_refine.py's small generators: one-pivot fronts
+The systems are nd_support.py's, as in test_gpu_nd_refine.py: one-pivot fronts
 (g5-leaf1), several levels (g11-leaf8), multi-tile fronts (g40-leaf256), fronts
 without pivots (blocks) and an irregular tree (random); the right-hand sides
 are orc.gen_x_cols(2001, n, 3).
@@ -23,96 +23,14 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, PcgInfo, _lib, cholesky_nd
+from nd_support import (_scale, assert_same, cols_of, coords, default_tol, matrix, omega_np, rel_err, rhs, rhs_cols,
+                        same_bits, setup, sym_dense, system)
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-10
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+SYSTEMS = ["g5-leaf1", "g11-leaf8", "g40-leaf256", "blocks", "random"]
 F32, F64 = np.float32, np.float64
-
-
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, leaf or None), built once."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
-    if name == "blocks":  # fronts with np == 0
-        import scipy.sparse as sp
-
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    rng = np.random.default_rng(7)  # an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, None
-
-
-@functools.lru_cache(maxsize=None)
-def _coords(name):
-    n, rp, ci, _, _ = _system(name)
-    return np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
-def _rhs(name):
-    from oracle import pyoracle as orc
-
-    return tuple(np.asarray(c, dtype=np.float64) for c in orc.gen_x_cols(2001, _system(name)[0], 3))
-
-
-def sym_dense(name, v):
-    """S as the library defines it, dense f64: the stored entries with column <= row, mirrored."""
-    n = _system(name)[0]
-    r, c = _coords(name)
-    low = np.zeros((n, n))
-    keep = c <= r
-    low[r[keep], c[keep]] = np.asarray(v, dtype=np.float64)[keep]
-    return low + np.tril(low, -1).T
-
-
-def default_tol(S):
-    return (int((S != 0).sum(axis=1).max()) + 2) * 2.0 ** -53
-
-
-def omega_np(S, x, b):
-    """The backward error from a longdouble residual."""
-    L = np.longdouble
-    r = np.asarray(b, L) - np.asarray(S, L) @ np.asarray(x, L)
-    return float(np.abs(r).max() / (np.abs(S).sum(axis=1).max() * np.abs(np.asarray(x, L)).max() + np.abs(b).max()))
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,12 +38,12 @@ def _truth(name, variant="A"):
     """(values, S, tol, the f64 solutions of S x = b) of a variant of the system's matrix."""
     v = variant_values(name, variant)
     S = sym_dense(name, v)
-    return v, S, default_tol(S), np.linalg.solve(S, np.stack(_rhs(name), axis=1))
+    return v, S, default_tol(S), np.linalg.solve(S, np.stack(rhs_cols(name), axis=1))
 
 
 def variant_values(name, variant):
-    n, _, _, v, _ = _system(name)
-    r, c = _coords(name)
+    n, _, _, v, _ = system(name)
+    r, c = coords(name)
     if variant == "A":
         return v
     if variant == "3A":
@@ -141,32 +59,6 @@ def variant_values(name, variant):
     raise KeyError(variant)
 
 
-def setup(monkeypatch, name):
-    leaf = _system(name)[4]
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-
-
-def matrix(name, dtype, v=None):
-    """A fresh Csr (a fresh device handle) of the pattern, with the system's values or v."""
-    n, rp, ci, v0, _ = _system(name)
-    return Csr.from_csr_arrays((n, n), rp, ci, np.asarray(v0 if v is None else v).astype(dtype))
-
-
-def rhs(name, dtype, k=3):
-    return Dense.from_columns([c.astype(dtype) for c in _rhs(name)[:k]])
-
-
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
-
-
 def result_parts(x, info):
     return cols_of(x) + [info.iters, info.berr, info.breakdown]
 
@@ -176,7 +68,7 @@ def assert_solved(name, variant, x, info, what):
     _, S, tol, xt = _truth(name, variant)
     assert isinstance(info, PcgInfo) and info.tol == tol and x.dtype == np.dtype(F64)
     for j, xj in enumerate(cols_of(x)):
-        w = omega_np(S, xj, _rhs(name)[j])
+        w = omega_np(S, xj, rhs_cols(name)[j])
         e = rel_err(xj, xt[:, j])
         print(f"{what} {name} {variant} column {j}: iters {info.iters[j]} berr {info.berr[j]:.3e} "
               f"omega {w:.3e} rel_err {e:.3e}")
@@ -189,18 +81,13 @@ def assert_solved(name, variant, x, info, what):
 # ---- the loop, emulated: np.linalg.cholesky in the factor's dtype stands for M -----------
 
 
-def _scale(v):
-    m = np.abs(v).max()
-    return 2.0 ** np.floor(np.log2(m)) if m > 0 and np.isfinite(m) else 1.0
-
-
 @functools.lru_cache(maxsize=None)
 def emulated_iters(name, variant, fdtype, max_iter=30):
     """The CG steps each column takes in a numpy run of the library's loop."""
     from scipy.linalg import solve_triangular
 
     _, S, tol, _ = _truth(name, variant)
-    Lf = np.linalg.cholesky(sym_dense(name, _system(name)[3]).astype(fdtype))
+    Lf = np.linalg.cholesky(sym_dense(name, system(name)[3]).astype(fdtype))
     snorm = np.abs(S).sum(axis=1).max()
 
     def minv(v):
@@ -210,7 +97,7 @@ def emulated_iters(name, variant, fdtype, max_iter=30):
         return s * solve_triangular(Lf.T, y, lower=False).astype(np.float64)
 
     out = []
-    for b in _rhs(name):
+    for b in rhs_cols(name):
         bn = np.abs(b).max()
 
         def omega(r, x):
@@ -318,7 +205,7 @@ def test_no_step_is_the_refined_solves_first_iterate(monkeypatch, name, dtype, f
 def test_columns_are_independent_and_calls_repeat(monkeypatch, name):
     """A/2 on the f32 factor of A, so that several steps run."""
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     A2 = matrix(name, F64, variant_values(name, "A/2"))
     with cholesky_nd(matrix(name, F64), factor_dtype=F32) as f:
         x3, i3 = f.solve_pcg(A2, rhs(name, F64))
@@ -326,10 +213,10 @@ def test_columns_are_independent_and_calls_repeat(monkeypatch, name):
         assert i3.converged.all() and (i3.iters >= 2).all()
         assert_same(result_parts(x3, i3), result_parts(*f.solve_pcg(A2, rhs(name, F64))))
         for j in range(3):
-            x1, i1 = f.solve_pcg(A2, Dense.from_columns([_rhs(name)[j]]))
+            x1, i1 = f.solve_pcg(A2, Dense.from_columns([rhs_cols(name)[j]]))
             assert same_bits(x1.get_col(0), x3.get_col(j)), j
             assert i1.iters[0] == i3.iters[j] and same_bits(i1.berr[:1], i3.berr[j:j + 1]), j
-        xz, iz = f.solve_pcg(A2, Dense.from_columns([np.zeros(n), _rhs(name)[0]]))  # beside a zero column
+        xz, iz = f.solve_pcg(A2, Dense.from_columns([np.zeros(n), rhs_cols(name)[0]]))  # beside a zero column
         assert not np.asarray(xz.get_col(0)).any() and iz.iters[0] == 0 and iz.berr[0] == 0.0 and iz.converged[0]
         assert same_bits(xz.get_col(1), x3.get_col(0)) and iz.iters[1] == i3.iters[0]
         assert same_bits(iz.berr[1:], i3.berr[:1])
@@ -344,16 +231,16 @@ def test_a_column_beside_one_that_converges_at_x0(monkeypatch, name):
     (cond(A) 2^-53, hence tol = 1e-12 for both columns), while the other
     column takes steps."""
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     v = variant_values(name, "diag40")
-    y = np.array(_rhs(name)[2])
+    y = np.array(rhs_cols(name)[2])
     y[[1, n // 2, n - 2]] = 0.0
-    b0 = sym_dense(name, _system(name)[3]) @ y
+    b0 = sym_dense(name, system(name)[3]) @ y
     A2 = matrix(name, F64, v)
     with cholesky_nd(matrix(name, F64)) as f:
-        x, info = f.solve_pcg(A2, Dense.from_columns([b0, _rhs(name)[0]]), tol=1e-12)
-        x1, i1 = f.solve_pcg(A2, Dense.from_columns([_rhs(name)[0]]), tol=1e-12)
-        xs, js = f.solve_pcg(A2, Dense.from_columns([_rhs(name)[0], b0]), tol=1e-12)
+        x, info = f.solve_pcg(A2, Dense.from_columns([b0, rhs_cols(name)[0]]), tol=1e-12)
+        x1, i1 = f.solve_pcg(A2, Dense.from_columns([rhs_cols(name)[0]]), tol=1e-12)
+        xs, js = f.solve_pcg(A2, Dense.from_columns([rhs_cols(name)[0], b0]), tol=1e-12)
     print(name, info, i1)
     assert info.converged.all() and info.iters[0] == 0 and info.iters[1] >= 2
     assert same_bits(x.get_col(1), x1.get_col(0)) and info.iters[1] == i1.iters[0]
@@ -375,7 +262,7 @@ def test_breakdown_on_a_negative_definite_system(monkeypatch):
 def test_the_upper_triangle_is_ignored(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    r, c = _coords(name)
+    r, c = coords(name)
     v = variant_values(name, "A/2")
     junk = np.where(c > r, 1e6 * (1.0 + np.arange(v.size)), v)
     with cholesky_nd(matrix(name, F64), factor_dtype=F32) as f:
@@ -386,13 +273,14 @@ def test_the_upper_triangle_is_ignored(monkeypatch):
 def test_edge_cases(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     A = matrix(name, F64)
     with cholesky_nd(A, factor_dtype=F32) as f:
-        x, info = f.solve_pcg(A, Dense.from_columns([_rhs(name)[0], np.zeros(n)]))  # a zero column beside a real one
+        # a zero column beside a real one
+        x, info = f.solve_pcg(A, Dense.from_columns([rhs_cols(name)[0], np.zeros(n)]))
         assert not np.asarray(x.get_col(1)).any() and info.berr[1] == 0.0 and info.iters[1] == 0
         assert info.converged[1] and not info.breakdown[1]
-        x1, i1 = f.solve_pcg(A, Dense.from_columns([_rhs(name)[0]]))
+        x1, i1 = f.solve_pcg(A, Dense.from_columns([rhs_cols(name)[0]]))
         assert same_bits(x.get_col(0), x1.get_col(0)) and info.iters[0] == i1.iters[0]
         x0, i0 = f.solve_pcg(A, Dense(0, n, []))  # k = 0
         assert x0.get_dims().cols == 0 and i0.iters.size == 0 and i0.berr.size == 0 and i0.breakdown.size == 0
@@ -403,9 +291,9 @@ def test_edge_cases(monkeypatch):
         with pytest.raises(TypeError):
             f.solve_pcg(A, rhs(name, F32))
         with pytest.raises(TypeError):
-            f.solve_pcg(matrix(name, np.int32, np.ones(_system(name)[3].size)), rhs(name, F64))
-        bad = _system(name)[3].copy()
-        r, c = _coords(name)
+            f.solve_pcg(matrix(name, np.int32, np.ones(system(name)[3].size)), rhs(name, F64))
+        bad = system(name)[3].copy()
+        r, c = coords(name)
         e = int(np.nonzero((r == n // 2) & (c == n // 2))[0][0])
         bad[e] = -bad[e]
         with pytest.raises(_lib.BsmError):
@@ -433,7 +321,7 @@ def test_device_call_has_the_host_calls_bits(monkeypatch, env):
     with cholesky_nd(matrix(name, F64), factor_dtype=F32) as f:
         want = result_parts(*f.solve_pcg(A2, rhs(name, F64)))
         assert (want[3] >= 2).all()  # steps were made
-        b = torch.from_numpy(np.stack(_rhs(name), axis=1)).cuda().contiguous()
+        b = torch.from_numpy(np.stack(rhs_cols(name), axis=1)).cuda().contiguous()
         out, info = device.nd_factor_solve_pcg(f, A2, b)
         got = out.cpu().numpy()
         assert_same([np.ascontiguousarray(got[:, j]) for j in range(3)] + [info.iters, info.berr, info.breakdown], want)
@@ -441,7 +329,7 @@ def test_device_call_has_the_host_calls_bits(monkeypatch, env):
         assert same is b
         assert_same([np.ascontiguousarray(b.cpu().numpy()[:, j]) for j in range(3)]
                     + [info2.iters, info2.berr, info2.breakdown], want)
-        b1 = torch.from_numpy(_rhs(name)[1].copy()).cuda()  # (n,): one column
+        b1 = torch.from_numpy(rhs_cols(name)[1].copy()).cuda()  # (n,): one column
         out1, info1 = device.nd_factor_solve_pcg(f, A2, b1)
         assert same_bits(out1.cpu().numpy(), want[1]) and info1.iters[0] == want[3][1]
         assert same_bits(info1.berr, want[4][1:2])

@@ -3,7 +3,7 @@ dtype is chosen (cholesky_nd(a, factor_dtype=...), bsm_nd_factor_create_as)
 and iterative refinement on it (NdFactor.solve_refined,
 device.nd_factor_solve_refined).
 
-The systems restate test_gpu_nd_factor_ops.py's small generators, the smallest
+The systems are nd_support.py's, the smallest
 that hit one-pivot fronts (g5-leaf1), several levels (g11-leaf8), multi-tile
 fronts (g40-leaf256), fronts without pivots (blocks) and an irregular tree
 (random); the right-hand sides are orc.gen_x_cols(2001, n, 3).
@@ -21,134 +21,23 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, _lib, cholesky_nd
+from nd_support import (assert_same, cols_of, coords, csr_parts, default_tol, matrix, omega_np, rel_err, rhs, rhs_cols,
+                        same_bits, setup, sym_dense, system)
 
 pytestmark = pytest.mark.gpu
 
 TOL = {np.float64: 1e-10, np.float32: 2e-3}
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+POISSON = ["g5-leaf1", "g11-leaf8", "g40-leaf256"]
+SYSTEMS = POISSON + ["blocks", "random"]
 F32, F64 = np.float32, np.float64
-
-
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, leaf or None), built once."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
-    if name == "blocks":  # fronts with np == 0
-        import scipy.sparse as sp
-
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    rng = np.random.default_rng(7)  # an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, None
-
-
-@functools.lru_cache(maxsize=None)
-def _coords(name):
-    n, rp, ci, _, _ = _system(name)
-    return np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
-def _rhs(name):
-    from oracle import pyoracle as orc
-
-    return tuple(np.asarray(c, dtype=np.float64) for c in orc.gen_x_cols(2001, _system(name)[0], 3))
-
-
-def sym_dense(name, v):
-    """S as the library defines it, dense f64: the stored entries with column <= row, mirrored."""
-    n = _system(name)[0]
-    r, c = _coords(name)
-    low = np.zeros((n, n))
-    keep = c <= r
-    low[r[keep], c[keep]] = np.asarray(v, dtype=np.float64)[keep]
-    return low + np.tril(low, -1).T
-
-
-def default_tol(S):
-    return (int((S != 0).sum(axis=1).max()) + 2) * 2.0 ** -53
-
-
-def omega_np(S, x, b):
-    """The backward error from a longdouble residual."""
-    L = np.longdouble
-    r = np.asarray(b, L) - np.asarray(S, L) @ np.asarray(x, L)
-    return float(np.abs(r).max() / (np.abs(S).sum(axis=1).max() * np.abs(np.asarray(x, L)).max() + np.abs(b).max()))
 
 
 @functools.lru_cache(maxsize=None)
 def _truth(name, dtype):
     """(S, tol, the f64 solutions of S x = b) for the system's values and right-hand sides rounded to dtype."""
-    S = sym_dense(name, _system(name)[3].astype(dtype))
-    B = np.stack([c.astype(dtype).astype(np.float64) for c in _rhs(name)], axis=1)
+    S = sym_dense(name, system(name)[3].astype(dtype))
+    B = np.stack([c.astype(dtype).astype(np.float64) for c in rhs_cols(name)], axis=1)
     return S, default_tol(S), np.linalg.solve(S, B)
-
-
-def setup(monkeypatch, name):
-    leaf = _system(name)[4]
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-
-
-def matrix(name, dtype, v=None):
-    """A fresh Csr (a fresh device handle) of the pattern, with the system's values or v."""
-    n, rp, ci, v0, _ = _system(name)
-    return Csr.from_csr_arrays((n, n), rp, ci, np.asarray(v0 if v is None else v).astype(dtype))
-
-
-def rhs(name, dtype, k=3):
-    return Dense.from_columns([c.astype(dtype) for c in _rhs(name)[:k]])
-
-
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
-
-
-def csr_parts(m):
-    return [np.asarray(m.row_index).copy(), np.asarray(m.col_index).copy(), np.asarray(m.v).copy()]
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
 
 
 def result_parts(x, info):
@@ -168,7 +57,7 @@ def test_f32_factor_refines_an_f64_system_to_f64_accuracy(monkeypatch, name):
         x, info = f.solve_refined(A, rhs(name, F64))
     assert x.dtype == np.dtype(F64) and info.tol == tol
     for j, xj in enumerate(cols_of(x)):
-        w = omega_np(S, xj, _rhs(name)[j])
+        w = omega_np(S, xj, rhs_cols(name)[j])
         e = rel_err(xj, xt[:, j])
         print(f"{name} column {j}: iters {info.iters[j]} berr {info.berr[j]:.3e} omega {w:.3e} rel_err {e:.3e}")
         assert info.converged[j] and info.iters[j] <= 3
@@ -197,8 +86,8 @@ def test_f32_factor_has_half_the_bytes(monkeypatch):
 def test_refactor_converts_and_keeps_the_source_dtype(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    n, _, _, v, _ = _system(name)
-    r, c = _coords(name)
+    n, _, _, v, _ = system(name)
+    r, c = coords(name)
     d = 1.0 + np.random.default_rng(11).random(n)
     v2 = d[r] * v * d[c]  # A2 = D A D
     b = rhs(name, F32)
@@ -215,7 +104,7 @@ def test_refactor_converts_and_keeps_the_source_dtype(monkeypatch):
 # ---- the refined solve ---------------------------------------------------------------
 
 
-@pytest.mark.parametrize("name", list(POISSON))
+@pytest.mark.parametrize("name", POISSON)
 def test_f32_system_is_solved_to_the_rounding_of_x(monkeypatch, name):
     setup(monkeypatch, name)
     _, _, xt = _truth(name, F32)
@@ -272,7 +161,7 @@ def test_columns_are_independent_and_calls_repeat(monkeypatch, name):
         again = f.solve_refined(A, rhs(name, F64))
         assert_same(result_parts(x3, i3), result_parts(*again))
         for j in range(3):
-            x1, i1 = f.solve_refined(A, Dense.from_columns([_rhs(name)[j]]))
+            x1, i1 = f.solve_refined(A, Dense.from_columns([rhs_cols(name)[j]]))
             assert same_bits(x1.get_col(0), x3.get_col(j)), j
             assert i1.iters[0] == i3.iters[j] and same_bits(i1.berr[:1], i3.berr[j:j + 1]), j
 
@@ -280,13 +169,13 @@ def test_columns_are_independent_and_calls_repeat(monkeypatch, name):
 def test_stale_factor(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    n, _, _, v, _ = _system(name)
-    r, c = _coords(name)
+    n, _, _, v, _ = system(name)
+    r, c = coords(name)
     v2 = v + 0.01 * (r == c)  # A + 0.01 I on A's factor
     S = sym_dense(name, v2)
     A2 = matrix(name, F64, v2)
     b = rhs(name, F64)
-    xt = np.linalg.solve(S, np.stack(_rhs(name), axis=1))
+    xt = np.linalg.solve(S, np.stack(rhs_cols(name), axis=1))
     with cholesky_nd(matrix(name, F64)) as f:
         x, info = f.solve_refined(A2, b, max_iter=30)
         print(info)
@@ -297,7 +186,7 @@ def test_stale_factor(monkeypatch):
     x3, i3 = upto[3]
     assert not i3.converged.any() and (i3.iters == 3).all()
     for j in range(3):
-        seen = [omega_np(S, np.asarray(xi.get_col(j)), _rhs(name)[j]) for xi, _ in upto]
+        seen = [omega_np(S, np.asarray(xi.get_col(j)), rhs_cols(name)[j]) for xi, _ in upto]
         print(f"column {j}: berr {i3.berr[j]:.6e}, the four iterates' omega {seen}")
         assert abs(i3.berr[j] - min(seen)) <= 1e-6 * min(seen)
         assert i3.berr[j] < upto[0][1].berr[j]
@@ -306,7 +195,7 @@ def test_stale_factor(monkeypatch):
 def test_divergence_keeps_the_best_iterate(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    A3 = matrix(name, F64, 3.0 * _system(name)[3])
+    A3 = matrix(name, F64, 3.0 * system(name)[3])
     b = rhs(name, F64)
     with cholesky_nd(matrix(name, F64)) as f:
         x0, i0 = f.solve_refined(A3, b, max_iter=0)
@@ -319,8 +208,8 @@ def test_divergence_keeps_the_best_iterate(monkeypatch):
 def test_the_upper_triangle_is_ignored(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    r, c = _coords(name)
-    v = _system(name)[3]
+    r, c = coords(name)
+    v = system(name)[3]
     junk = np.where(c > r, 1e6 * (1.0 + np.arange(v.size)), v)
     A = matrix(name, F64)
     with cholesky_nd(A, factor_dtype=F32) as f:
@@ -331,17 +220,18 @@ def test_the_upper_triangle_is_ignored(monkeypatch):
 def test_edge_cases(monkeypatch):
     name = "g11-leaf8"
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     A = matrix(name, F64)
     with cholesky_nd(A, factor_dtype=F32) as f:
-        x, info = f.solve_refined(A, Dense.from_columns([_rhs(name)[0], np.zeros(n)]))  # a zero column beside a real one
+        # a zero column beside a real one
+        x, info = f.solve_refined(A, Dense.from_columns([rhs_cols(name)[0], np.zeros(n)]))
         assert not np.asarray(x.get_col(1)).any() and info.berr[1] == 0.0 and info.iters[1] == 0 and info.converged[1]
-        x1, i1 = f.solve_refined(A, Dense.from_columns([_rhs(name)[0]]))
+        x1, i1 = f.solve_refined(A, Dense.from_columns([rhs_cols(name)[0]]))
         assert same_bits(x.get_col(0), x1.get_col(0)) and info.iters[0] == i1.iters[0]
         x0, i0 = f.solve_refined(A, Dense(0, n, []))  # k = 0
         assert x0.get_dims().cols == 0 and i0.iters.size == 0 and i0.berr.size == 0
-        bad = _system(name)[3].copy()
-        r, c = _coords(name)
+        bad = system(name)[3].copy()
+        r, c = coords(name)
         e = int(np.nonzero((r == n // 2) & (c == n // 2))[0][0])
         bad[e] = -bad[e]
         with pytest.raises(_lib.BsmError):
@@ -368,13 +258,13 @@ def test_device_call_has_the_host_calls_bits(monkeypatch, env):
     A = matrix(name, F64)
     with cholesky_nd(A, factor_dtype=F32) as f:
         want = result_parts(*f.solve_refined(A, rhs(name, F64)))
-        b = torch.from_numpy(np.stack(_rhs(name), axis=1)).cuda().contiguous()
+        b = torch.from_numpy(np.stack(rhs_cols(name), axis=1)).cuda().contiguous()
         out, info = device.nd_factor_solve_refined(f, A, b)
         got = out.cpu().numpy()
         assert_same([np.ascontiguousarray(got[:, j]) for j in range(3)] + [info.iters, info.berr], want)
         same, info2 = device.nd_factor_solve_refined(f, A, b, out=b)  # in place
         assert same is b
         assert_same([np.ascontiguousarray(b.cpu().numpy()[:, j]) for j in range(3)] + [info2.iters, info2.berr], want)
-        b1 = torch.from_numpy(_rhs(name)[1].copy()).cuda()  # (n,): one column
+        b1 = torch.from_numpy(rhs_cols(name)[1].copy()).cuda()  # (n,): one column
         out1, info1 = device.nd_factor_solve_refined(f, A, b1)
         assert same_bits(out1.cpu().numpy(), want[1]) and info1.iters[0] == want[3][1]

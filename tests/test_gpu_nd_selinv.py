@@ -2,8 +2,8 @@
 inv_entries / inv_on, device.nd_factor_inv_diag): Z = A^-1 on the pattern of
 L + L^T by the Takahashi recursion over the fronts.
 
-The systems are those of test_gpu_nd_factor_ops.py, the smallest that reach
-each structure: one-pivot fronts with 63 padding pivots (g5-leaf1), a single
+The systems are nd_support.py's, the ones test_gpu_nd_factor_ops.py runs: the
+smallest that reach each structure: one-pivot fronts with 63 padding pivots (g5-leaf1), a single
 dense front of two pivot tiles (g11-onefront), several levels with a parent
 more than one level above a child (g40-leaf64), leaves of several pivot tiles
 (g40-leaf256), fronts with np = 0 (blocks), an irregular tree (random); f64 on
@@ -26,14 +26,14 @@ import threading
 import numpy as np
 import pytest
 
+import nd_support
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, MatErrKind, _lib, cholesky_nd
+from nd_support import assert_same, cols_of, coords, dense_of, same_bits, setup, system
 
 pytestmark = pytest.mark.gpu
 
-# (g, BSM_ND_LEAF) of orc.poisson2d(g)
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g11-onefront": (11, "100000"), "g40-leaf64": (40, "64"),
-           "g40-leaf256": (40, "256")}
-SYSTEMS = list(POISSON) + ["blocks", "random"]
+POISSON = ["g5-leaf1", "g11-leaf8", "g11-onefront", "g40-leaf64", "g40-leaf256"]
+SYSTEMS = POISSON + ["blocks", "random"]
 CASES = [(s, np.float64) for s in SYSTEMS] + [(s, np.float32) for s in POISSON]
 CASE_IDS = [f"{s}-{np.dtype(d).name}" for s, d in CASES]
 FEW = [("g5-leaf1", np.float32), ("g11-onefront", np.float64), ("g40-leaf256", np.float64), ("blocks", np.float64)]
@@ -41,62 +41,11 @@ FEW_IDS = [f"{s}-{np.dtype(d).name}" for s, d in FEW]
 MARGIN = 8.0
 
 
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def dense_of(rp, ci, v, n):
-    a = np.zeros((n, n), dtype=np.float64)
-    rows = np.repeat(np.arange(n), np.diff(np.asarray(rp).astype(np.int64)))
-    a[rows, np.asarray(ci).astype(np.int64)] = np.asarray(v, dtype=np.float64)
-    return a
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, rp, ci, v as f64, leaf or None), built once."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        return g * g, rp, ci, np.asarray(v, dtype=np.float64), leaf
-    if name == "blocks":  # fronts with np == 0
-        import scipy.sparse as sp
-
-        g = 12
-        rp, ci, v = orc.poisson2d(g)
-        P = sp.csr_matrix((v, ci.astype(np.int64), rp.astype(np.int64)), shape=(g * g, g * g))
-        M = sp.block_diag([P, 2.0 * P, sp.identity(9) * 3.0], format="csr")
-        M.sort_indices()
-        return M.shape[0], M.indptr.astype(np.uint64), M.indices.astype(np.uint64), M.data.astype(np.float64), None
-    rng = np.random.default_rng(7)  # an irregular tree
-    n = 300
-    a = np.zeros((n, n))
-    mask = rng.random((n, n)) < 0.02
-    vals = rng.uniform(-1.0, 1.0, (n, n))
-    a[mask] = vals[mask]
-    a = np.tril(a, -1)
-    a = a + a.T
-    a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
-    rp, ci, v = csr_arrays(a)
-    return n, rp, ci, v, None
-
-
 @functools.lru_cache(maxsize=None)
 def _second_values(name):
     """A2 = D A D's values, d = 1 + rng.random(n): SPD with A; and A's with one diagonal entry negated."""
-    n, rp, ci, v, _ = _system(name)
-    rows = np.repeat(np.arange(n), np.diff(rp.astype(np.int64)))
-    cols = ci.astype(np.int64)
+    n, _, _, v, _ = system(name)
+    rows, cols = coords(name)
     d = 1.0 + np.random.default_rng(11).random(n)
     bad = v.copy()
     e = int(np.nonzero((rows == n // 2) & (cols == n // 2))[0][0])
@@ -107,27 +56,14 @@ def _second_values(name):
 @functools.lru_cache(maxsize=None)
 def _zref(name, dtype):
     """inv(A) in f64 of the matrix as the factor sees it (its values rounded to dtype). Never modified."""
-    n, rp, ci, v, _ = _system(name)
+    n, rp, ci, v, _ = system(name)
     z = np.linalg.inv(dense_of(rp, ci, v.astype(dtype), n))
     z.setflags(write=False)
     return z
 
 
-def setup(monkeypatch, name):
-    leaf = _system(name)[4]
-    if leaf is not None:
-        monkeypatch.setenv("BSM_ND_LEAF", leaf)
-
-
 def matrix(name, dtype, which=0):
-    n, rp, ci, v, _ = _system(name)
-    vals = v if which == 0 else _second_values(name)[which - 1]
-    return Csr.from_csr_arrays((n, n), rp, ci, vals.astype(dtype))
-
-
-def a_pairs(name):
-    n, rp, ci, _, _ = _system(name)
-    return np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)
+    return nd_support.matrix(name, dtype, None if which == 0 else _second_values(name)[which - 1])
 
 
 def l_pairs(f):
@@ -139,20 +75,10 @@ def l_pairs(f):
     return p[rows], p[np.asarray(l.col_index).astype(np.int64)]
 
 
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
-
-
 def everything(f, name):
     """inv_diag, inv_on(A)'s values and the whole pattern of L through inv_entries."""
     li, lj = l_pairs(f)
     return [f.inv_diag(), np.asarray(f.inv_on(matrix(name, f.dtype)).v).copy(), f.inv_entries(li, lj)]
-
-
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
 
 
 # ---- accuracy -------------------------------------------------------------------
@@ -161,7 +87,7 @@ def assert_same(got, want):
 @pytest.mark.parametrize("name,dtype", CASES, ids=CASE_IDS)
 def test_accuracy_against_the_factors_own_solves(monkeypatch, name, dtype):
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     zref = _zref(name, dtype)
     scale = np.abs(zref).max()
     with cholesky_nd(matrix(name, dtype)) as f:
@@ -170,11 +96,11 @@ def test_accuracy_against_the_factors_own_solves(monkeypatch, name, dtype):
                       axis=1).astype(np.float64)  # xs[:, j] = A^-1 e_j
         d = f.inv_diag()
         assert d.dtype == np.dtype(dtype) and d.shape == (n,)
-        ai, aj = a_pairs(name)
+        ai, aj = coords(name)
         on = f.inv_on(matrix(name, dtype))
         assert on.dtype == np.dtype(dtype) and on.is_finalised
-        assert np.array_equal(np.asarray(on.row_index), _system(name)[1])
-        assert np.array_equal(np.asarray(on.col_index), _system(name)[2])
+        assert np.array_equal(np.asarray(on.row_index), system(name)[1])
+        assert np.array_equal(np.asarray(on.col_index), system(name)[2])
         li, lj = l_pairs(f)
         le = f.inv_entries(li, lj)
         assert le.dtype == np.dtype(dtype) and le.shape == li.shape
@@ -195,7 +121,7 @@ def test_accuracy_against_the_factors_own_solves(monkeypatch, name, dtype):
 def test_one_dense_front_answers_every_pair(monkeypatch):
     name, dtype = "g11-onefront", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     zref = _zref(name, dtype)
     i, j = (x.ravel() for x in np.meshgrid(np.arange(n), np.arange(n), indexing="ij"))
     with cholesky_nd(matrix(name, dtype)) as f:
@@ -207,7 +133,7 @@ def test_one_dense_front_answers_every_pair(monkeypatch):
 def test_pairs_outside_the_pattern_and_out_of_bounds(monkeypatch):
     name, dtype = "g11-leaf8", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     with cholesky_nd(matrix(name, dtype)) as f:
         li, lj = l_pairs(f)
         stored = np.zeros((n, n), dtype=bool)
@@ -246,7 +172,7 @@ def test_inv_on_takes_the_pattern_of_its_argument(monkeypatch):
     """The pattern is a's own (here the diagonal alone, stored zeros included), not the factored matrix's."""
     name, dtype = "blocks", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     with cholesky_nd(matrix(name, dtype)) as f:
         d = f.inv_diag()
         eye = Csr.from_csr_arrays((n, n), np.arange(n + 1, dtype=np.uint64), np.arange(n, dtype=np.uint64),
@@ -266,7 +192,7 @@ def test_same_bits_on_every_call_and_route(monkeypatch, name, dtype):
     from basic_sparse_matrix_amd import device
 
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     with cholesky_nd(matrix(name, dtype)) as f:
         base = everything(f, name)
         assert_same(everything(f, name), base)
@@ -294,7 +220,7 @@ def test_device_diag_checks(monkeypatch):
 
     name, dtype = "g5-leaf1", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     with cholesky_nd(matrix(name, dtype)) as f:
         with pytest.raises(TypeError):
             device.nd_factor_inv_diag(f, torch.zeros(n, dtype=torch.float32, device="cuda"))
@@ -326,7 +252,7 @@ def test_nothing_undefined_is_read(monkeypatch, name, dtype):
 @pytest.mark.parametrize("name,dtype", FEW, ids=FEW_IDS)
 def test_the_factor_is_untouched(monkeypatch, name, dtype):
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     rng = np.random.default_rng(3)
     b = [rng.standard_normal(n).astype(dtype) for _ in range(3)]
 
@@ -351,7 +277,7 @@ def test_a_handle_without_values_refuses(monkeypatch):
 
     name, dtype = "g40-leaf64", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     A = matrix(name, dtype)
     with cholesky_nd(A) as f:
         base = f.inv_diag()
@@ -384,7 +310,7 @@ def test_a_second_thread_solves_while_the_selected_inverse_runs(monkeypatch):
     """One solve on another thread: the handle's mutex puts it before or after the selected inverse."""
     name, dtype = "g40-leaf64", np.float64
     setup(monkeypatch, name)
-    n = _system(name)[0]
+    n = system(name)[0]
     B = Dense.from_columns([np.random.default_rng(5).standard_normal(n)])
     with cholesky_nd(matrix(name, dtype)) as f:
         ref, base = cols_of(f.solve(B)), f.inv_diag()

@@ -7,7 +7,7 @@ order. So the contract is EQUALITY with f.solve on the densified b
 (np.array_equal: a zero's sign is the one thing a skipped front can change);
 nothing here has a tolerance.
 
-The systems are test_gpu_nd_updown.py's with their BSM_ND_LEAF, rebuilt here:
+The systems are nd_support.dense_system's with their BSM_ND_LEAF:
   g5-leaf1     one pivot beside 63 padding pivots; a path over every level
   g11-leaf8    two entries of one column in different leaves that meet at an
                ancestor; an entry that starts in a separator; a requested row
@@ -33,11 +33,10 @@ import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, MatErrKind, _lib, cholesky_nd
 from basic_sparse_matrix_amd.solver import nd_analyse
+from nd_support import csr_arrays, dense_matrix, dense_setup, dense_system, same_bits
 
 gpu = pytest.mark.gpu
 
-# (g, BSM_ND_LEAF) of orc.poisson2d(g)
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
 SYSTEMS = ("g5-leaf1", "g11-leaf8", "g40-leaf256", "blocks")
 KS = (1, 3, 33)
 # (the matrix's dtype, the factor's)
@@ -49,45 +48,9 @@ FEW = [("g5-leaf1", 3, DTYPES[2]), ("g11-leaf8", 33, DTYPES[0]), ("g40-leaf256",
 FEW_IDS = [f"{s}-k{k}-{np.dtype(d[0]).name}-factor-{np.dtype(d[1]).name}" for s, k, d in FEW]
 
 
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=a.shape[0]))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, S dense f64, the leaf for the analysis, BSM_ND_LEAF), built once. Never modified."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        n = g * g
-        s = np.zeros((n, n))
-        s[np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)] = v
-    else:  # blocks: two components and nine isolated vertices, so fronts with np == 0 join them
-        rp, ci, v = orc.poisson2d(12)
-        p = np.zeros((144, 144))
-        p[np.repeat(np.arange(144), np.diff(rp.astype(np.int64))), ci.astype(np.int64)] = v
-        # BSM_ND_LEAF=64: at the default leaf the two grids are one leaf each and no front is empty
-        n, leaf = 2 * 144 + 9, "64"
-        s = np.zeros((n, n))
-        s[:144, :144] = p
-        s[144:288, 144:288] = 2.0 * p
-        s[288:, 288:] = 3.0 * np.eye(9)
-    s.setflags(write=False)
-    return n, s, int(leaf), leaf
-
-
 @functools.lru_cache(maxsize=None)
 def _tree(name):
-    n, s, leaf, _ = _system(name)
+    n, s, leaf, _ = dense_system(name)
     rp, ci, _ = csr_arrays(s)
     t = nd_analyse(n, rp, ci, leaf=leaf)
     owner = np.zeros(n, dtype=np.int64)  # by NEW index
@@ -121,7 +84,7 @@ def reach(name, vertices):
 @functools.lru_cache(maxsize=None)
 def _places(name):
     """The vertices (A's order) the docstring names, from the host analysis."""
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     t = _tree(name)
     perm, start, end, level = t["perm"], t["start"], t["end"], t["level"]
     leaves = [i for i in range(len(start)) if level[i] == 0 and end[i] > start[i]]
@@ -149,7 +112,7 @@ def _places(name):
 @functools.lru_cache(maxsize=None)
 def columns(name, k):
     """b (n x k, f64 values that f32 holds exactly, no -0). Never modified."""
-    n = _system(name)[0]
+    n = dense_system(name)[0]
     p = _places(name)
     rng = np.random.default_rng(7 + k)
 
@@ -176,7 +139,7 @@ def columns(name, k):
 @functools.lru_cache(maxsize=None)
 def rows_of(name):
     """The rows asked for: unsorted, with repeats."""
-    n = _system(name)[0]
+    n = dense_system(name)[0]
     p = _places(name)
     rng = np.random.default_rng(11)
     r = [p["last"], p["sep"], p["a"]]
@@ -191,15 +154,6 @@ def rows_of(name):
 def b_csr(b, dtype):
     rp, ci, v = csr_arrays(b)
     return Csr.from_csr_arrays(b.shape, rp, ci, v.astype(dtype))
-
-
-def matrix(s, dtype):
-    rp, ci, v = csr_arrays(s)
-    return Csr.from_csr_arrays(s.shape, rp, ci, v.astype(dtype))
-
-
-def setup(monkeypatch, name):
-    monkeypatch.setenv("BSM_ND_LEAF", _system(name)[3])
 
 
 def arr(d):
@@ -258,13 +212,13 @@ def test_equality(monkeypatch, name, k, dtypes):
     """1 (equality, host and device, inv_block) and 3a (the counts are the unions of paths)."""
     from basic_sparse_matrix_amd import device
 
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     t = _tree(name)
     b, rows = columns(name, k), rows_of(name)
     bc = b_csr(b, fdt)
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
         assert np.array_equal(f.perm, t["perm"])  # the entries were chosen through this permutation
         want = dense_solve(f, b)
         assert want.dtype == np.dtype(fdt) and np.isfinite(want).all()
@@ -309,11 +263,11 @@ def test_equality(monkeypatch, name, k, dtypes):
 @pytest.mark.parametrize("name,k,dtypes", FEW, ids=FEW_IDS)
 def test_independence(monkeypatch, name, k, dtypes):
     """2: a value depends neither on the other rows asked for nor on the call's other columns, and repeats."""
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    s = _system(name)[1]
+    s = dense_system(name)[1]
     b, rows = columns(name, k), rows_of(name)
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
         base = arr(f.solve_sparse(b_csr(b, fdt), rows))
         assert same_bits(arr(f.solve_sparse(b_csr(b, fdt), rows)), base)
         full = arr(f.solve_sparse(b_csr(b, fdt)))
@@ -333,14 +287,14 @@ def test_nothing_undefined_is_read(monkeypatch, name, k, dtypes):
     """3b: BSM_ND_POISON=1 -- every temporary starts as NaN; the results are finite and unchanged."""
     from basic_sparse_matrix_amd import device
 
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    s = _system(name)[1]
+    s = dense_system(name)[1]
     b, rows = columns(name, k), rows_of(name)
     cols = np.nonzero(b.any(axis=1))[0][:3]
 
     def run():
-        with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+        with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
             bc = b_csr(b, fdt)
             return [arr(f.solve_sparse(bc, rows)), arr(f.solve_sparse(bc)), f.inv_block(rows, cols),
                     device.nd_factor_solve_sparse(f, bc, rows).cpu().numpy()]
@@ -357,14 +311,14 @@ def test_nothing_undefined_is_read(monkeypatch, name, k, dtypes):
 @pytest.mark.parametrize("name,k,dtypes", FEW, ids=FEW_IDS)
 def test_it_sees_the_current_factor(monkeypatch, name, k, dtypes):
     """4: after refactor(a2) and after update(w), equality with f.solve still holds."""
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     b, rows = columns(name, k), rows_of(name)
     bc = b_csr(b, fdt)
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
         x0 = arr(f.solve_sparse(bc, rows))
-        f.refactor(matrix(1.5 * s, src))
+        f.refactor(dense_matrix(1.5 * s, src))
         want = dense_solve(f, b)
         x1 = arr(f.solve_sparse(bc, rows))
         assert np.array_equal(x1, want[rows]) and not np.array_equal(x1, x0)
@@ -383,8 +337,8 @@ def test_refusals_leave_the_outputs_untouched(monkeypatch):
     import torch
 
     name, (src, fdt) = "g11-leaf8", DTYPES[0]
-    setup(monkeypatch, name)
-    n, s, _, _ = _system(name)
+    dense_setup(monkeypatch, name)
+    n, s, _, _ = dense_system(name)
     lib = _lib.require_device()
     cp = np.array([0, 2, 2, 3], dtype=np.uint64)
     br = np.array([3, 77, 5], dtype=np.uint64)
@@ -415,7 +369,7 @@ def test_refusals_leave_the_outputs_untouched(monkeypatch):
                 and bool((xt == sentinel).all()))
 
     u64 = lambda *v: np.array(v, dtype=np.uint64)  # noqa: E731
-    with cholesky_nd(matrix(s, src)) as f:
+    with cholesky_nd(dense_matrix(s, src)) as f:
         h = f.handle
         for call in (host, dev):
             inv, oob = _lib.BSM_ERR_INVALID, _lib.BSM_ERR_OUT_OF_BOUNDS
@@ -470,11 +424,11 @@ def test_refusals_leave_the_outputs_untouched(monkeypatch):
         bad = s.copy()
         bad[n // 2, n // 2] = -bad[n // 2, n // 2]
         with pytest.raises(_lib.BsmError, match="positive definite"):
-            f.refactor(matrix(bad, src))
+            f.refactor(dense_matrix(bad, src))
         for call in (host, dev):
             assert call(h) == _lib.BSM_ERR_INVALID and "refactor first" in _lib.last_error()
         assert untouched()
-        f.refactor(matrix(s, src))
+        f.refactor(dense_matrix(s, src))
         assert host(h) == _lib.BSM_OK
         want = dense_solve(f, _dense_of(cp, br, bv, n))
         assert np.array_equal(np.stack(xs, axis=1), want[xr.astype(np.int64)])

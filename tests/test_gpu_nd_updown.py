@@ -3,8 +3,8 @@ downdate, bsm_nd_factor_updown): f becomes the factor of
 P (S +- W W^T) P^T by rewriting only the fronts on the paths from W's columns
 to the root.
 
-The systems are test_gpu_nd_selinv.py's Poisson ones with their BSM_ND_LEAF,
-rebuilt here: one real pivot beside 63 padding pivots and a path across every
+The systems are nd_support.py's dense ones (dense_system) with their
+BSM_ND_LEAF: one real pivot beside 63 padding pivots and a path across every
 level (g5-leaf1), columns that start in different leaves and meet at an
 ancestor and one that starts in a separator (g11-leaf8), leaves of several
 pivot tiles (g40-leaf256), fronts with np = 0 on the path (blocks). The
@@ -33,11 +33,10 @@ import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, MatErrKind, _lib, cholesky_nd
 from basic_sparse_matrix_amd.solver import nd_analyse
+from nd_support import assert_same, cols_of, csr_arrays, dense_matrix, dense_setup, dense_system, same_bits
 
 gpu = pytest.mark.gpu
 
-# (g, BSM_ND_LEAF) of orc.poisson2d(g)
-POISSON = {"g5-leaf1": (5, "1"), "g11-leaf8": (11, "8"), "g40-leaf256": (40, "256")}
 KS = {"g5-leaf1": (1, 3), "g11-leaf8": (1, 3, 16), "g40-leaf256": (1, 3, 16), "blocks": (1, 3)}
 # (the matrix's dtype, the factor's)
 DTYPES = [(np.float64, np.float64), (np.float64, np.float32), (np.float32, np.float32)]
@@ -60,46 +59,9 @@ EMULATED_WORST = 7.44
 R = 2.0 * EMULATED_WORST
 
 
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def same_bits(x, y):
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
-    return x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8))
-
-
-@functools.lru_cache(maxsize=None)
-def _system(name):
-    """(n, S dense f64, the leaf for the analysis, BSM_ND_LEAF), built once. Never modified."""
-    from oracle import pyoracle as orc
-
-    if name in POISSON:
-        g, leaf = POISSON[name]
-        rp, ci, v = orc.poisson2d(g)
-        n = g * g
-        s = np.zeros((n, n))
-        s[np.repeat(np.arange(n), np.diff(rp.astype(np.int64))), ci.astype(np.int64)] = v
-    else:  # blocks: two components and nine isolated vertices, so fronts with np == 0 join them
-        rp, ci, v = orc.poisson2d(12)
-        p = np.zeros((144, 144))
-        p[np.repeat(np.arange(144), np.diff(rp.astype(np.int64))), ci.astype(np.int64)] = v
-        # BSM_ND_LEAF=64: at the default leaf the two grids are one leaf each and no front is empty
-        n, leaf = 2 * 144 + 9, "64"
-        s = np.zeros((n, n))
-        s[:144, :144] = p
-        s[144:288, 144:288] = 2.0 * p
-        s[288:, 288:] = 3.0 * np.eye(9)
-    s.setflags(write=False)
-    return n, s, int(leaf), leaf
-
-
 @functools.lru_cache(maxsize=None)
 def _tree(name):
-    n, s, leaf, _ = _system(name)
+    n, s, leaf, _ = dense_system(name)
     rp, ci, _ = csr_arrays(s)
     t = nd_analyse(n, rp, ci, leaf=leaf)
     owner = np.zeros(n, dtype=np.int64)
@@ -121,7 +83,7 @@ def path(name, node):
 @functools.lru_cache(maxsize=None)
 def _columns(name, k, sign):
     """W (n x k, f64 values that f32 holds exactly) for the system, chosen through the permutation."""
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     perm = _tree(name)["perm"]
     pinv = np.empty(n, dtype=np.int64)
     pinv[perm] = np.arange(n)
@@ -160,23 +122,8 @@ def _columns(name, k, sign):
 
 
 def w_csr(w, dtype):
-    rp, ci, v = csr_arrays_rect(w)
+    rp, ci, v = csr_arrays(w)
     return Csr.from_csr_arrays(w.shape, rp, ci, v.astype(dtype))
-
-
-def csr_arrays_rect(a):
-    nzr, nzc = np.nonzero(a != 0)
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=a.shape[0]))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
-
-
-def matrix(s, dtype):
-    rp, ci, v = csr_arrays(s)
-    return Csr.from_csr_arrays(s.shape, rp, ci, v.astype(dtype))
-
-
-def setup(monkeypatch, name):
-    monkeypatch.setenv("BSM_ND_LEAF", _system(name)[3])
 
 
 @functools.lru_cache(maxsize=None)
@@ -184,10 +131,6 @@ def _rhs(n):
     b = np.random.default_rng(5).standard_normal((n, 8))
     b.setflags(write=False)
     return b
-
-
-def cols_of(d):
-    return [np.asarray(d.get_col(j)).copy() for j in range(d.get_dims().cols)]
 
 
 def floor_of(s2, fdtype):
@@ -261,7 +204,7 @@ def dense_solve(l, perm, fdtype):
 def emulated_ratios(name, k, dtypes):
     """The three steps of test_accuracy on the CPU: the largest ratio of each."""
     src, fdt = dtypes
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     perm = _tree(name)["perm"]
     s = s.astype(src).astype(np.float64)
     out = {}
@@ -351,22 +294,16 @@ def solve_bits(f):
     return cols_of(f.solve(Dense.from_columns([np.ascontiguousarray(b[:, j]) for j in range(3)])))
 
 
-def assert_same(got, want):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert same_bits(g, w), i
-
-
 @gpu
 @pytest.mark.parametrize("name,k,dtypes", CASES, ids=CASE_IDS)
 def test_accuracy(monkeypatch, name, k, dtypes):
     """1 (accuracy of an update and of a downdate), 2 (logdet) and 3 (the round trip, then refactor)."""
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    n, s, _, _ = _system(name)
+    n, s, _, _ = dense_system(name)
     s = s.astype(src).astype(np.float64)
     wu, wd = _columns(name, k, +1), _columns(name, k, -1)
-    a = matrix(s, src)
+    a = dense_matrix(s, src)
     with cholesky_nd(a, factor_dtype=fdt) as f:
         assert np.array_equal(f.perm, _tree(name)["perm"])  # the columns were chosen through this permutation
         base_l = l_bits(f)
@@ -380,7 +317,7 @@ def test_accuracy(monkeypatch, name, k, dtypes):
         f.update(w_csr(wu, src))
         assert f.nnz_l == 0
         fl = floor_of(su, fdt)
-        with cholesky_nd(matrix(su, src), factor_dtype=fdt) as fresh:
+        with cholesky_nd(dense_matrix(su, src), factor_dtype=fdt) as fresh:
             mf = measures(np.stack(cols_of(fresh.solve(Dense.from_columns(
                 [np.ascontiguousarray(b[:, j]) for j in range(8)]))), axis=1), dense_l(fresh), fresh.perm, su)
             ld_fresh = fresh.logdet()
@@ -400,7 +337,7 @@ def test_accuracy(monkeypatch, name, k, dtypes):
         # a downdate against a fresh factor of S - W W^T
         sd = s - wd @ wd.T
         f.downdate(w_csr(wd, src))
-        with cholesky_nd(matrix(sd, src), factor_dtype=fdt) as fresh:
+        with cholesky_nd(dense_matrix(sd, src), factor_dtype=fdt) as fresh:
             mf = measures(np.stack(cols_of(fresh.solve(Dense.from_columns(
                 [np.ascontiguousarray(b[:, j]) for j in range(8)]))), axis=1), dense_l(fresh), fresh.perm, sd)
         check("downdate", gpu_measures(f, sd), mf, floor_of(sd, fdt))
@@ -410,21 +347,21 @@ def test_accuracy(monkeypatch, name, k, dtypes):
 @pytest.mark.parametrize("name,k,dtypes", FEW, ids=FEW_IDS)
 def test_bits(monkeypatch, name, k, dtypes):
     """4: the same call gives the same bits, whatever the factor's and the solves' switches."""
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    s = _system(name)[1].astype(src).astype(np.float64)
+    s = dense_system(name)[1].astype(src).astype(np.float64)
     wu = _columns(name, k, +1)
 
     def run():
-        with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+        with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
             f.update(w_csr(wu, src))
             return l_bits(f) + solve_bits(f) + [np.array([f.logdet()])]
 
     base = run()
     assert_same(run(), base)
-    with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:  # and on a handle that has been updated and put back
+    with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:  # and on a handle that has been updated and put back
         f.update(w_csr(wu, src))
-        f.refactor(matrix(s, src))
+        f.refactor(dense_matrix(s, src))
         f.update(w_csr(wu, src))
         assert_same(l_bits(f) + solve_bits(f) + [np.array([f.logdet()])], base)
     for mode in ("0", "1"):
@@ -440,16 +377,16 @@ def test_bits(monkeypatch, name, k, dtypes):
 @gpu
 def test_two_columns_repeat_their_bits(monkeypatch):
     name, (src, fdt) = "g11-leaf8", DTYPES[0]
-    setup(monkeypatch, name)
-    s = _system(name)[1]
+    dense_setup(monkeypatch, name)
+    s = dense_system(name)[1]
     w = _columns(name, 3, +1)[:, :2]
     out = []
     for _ in range(2):
-        with cholesky_nd(matrix(s, src)) as f:
+        with cholesky_nd(dense_matrix(s, src)) as f:
             f.update(w_csr(w, src))
             out.append(l_bits(f) + solve_bits(f))
     assert_same(out[1], out[0])
-    with cholesky_nd(matrix(s, src)) as f:  # two calls of one column: the same matrix
+    with cholesky_nd(dense_matrix(s, src)) as f:  # two calls of one column: the same matrix
         f.update(w_csr(w[:, :1], src))
         f.update(w_csr(w[:, 1:], src))
         s2 = s + w @ w.T
@@ -461,13 +398,13 @@ def test_two_columns_repeat_their_bits(monkeypatch):
 @pytest.mark.parametrize("name,k,dtypes", FEW, ids=FEW_IDS)
 def test_nothing_undefined_is_read(monkeypatch, name, k, dtypes):
     """7: BSM_ND_POISON=1 -- the work columns and the coefficients start as NaN (and the fronts before the factor)."""
-    setup(monkeypatch, name)
+    dense_setup(monkeypatch, name)
     src, fdt = dtypes
-    s = _system(name)[1].astype(src).astype(np.float64)
+    s = dense_system(name)[1].astype(src).astype(np.float64)
     wu, wd = _columns(name, k, +1), _columns(name, k, -1)
 
     def run():
-        with cholesky_nd(matrix(s, src), factor_dtype=fdt) as f:
+        with cholesky_nd(dense_matrix(s, src), factor_dtype=fdt) as f:
             f.update(w_csr(wu, src))
             out = l_bits(f) + solve_bits(f)
             f.downdate(w_csr(wu, src))
@@ -486,9 +423,9 @@ def test_nothing_undefined_is_read(monkeypatch, name, k, dtypes):
 def test_untouched_on_refusal(monkeypatch):
     """5: a refused call leaves the factor's bits and the handle valid."""
     name, (src, fdt) = "g11-leaf8", DTYPES[0]
-    setup(monkeypatch, name)
-    n, s, _, _ = _system(name)
-    a = matrix(s, src)
+    dense_setup(monkeypatch, name)
+    n, s, _, _ = dense_system(name)
+    a = dense_matrix(s, src)
     with cholesky_nd(a) as f:
         before = solve_bits(f) + l_bits(f) + [np.array([f.logdet()])]
         perm = f.perm
@@ -549,7 +486,7 @@ def test_untouched_on_refusal(monkeypatch):
         bad = s.copy()
         bad[n // 2, n // 2] = -bad[n // 2, n // 2]
         with pytest.raises(_lib.BsmError, match="positive definite"):
-            f.refactor(matrix(bad, src))
+            f.refactor(dense_matrix(bad, src))
         with pytest.raises(_lib.BsmError, match="refactor first"):
             f.update(w_csr(wbad[:, :1], src))
         f.refactor(a)
@@ -560,17 +497,17 @@ def test_untouched_on_refusal(monkeypatch):
 def test_everything_downstream_sees_the_new_factor(monkeypatch):
     """6: the selected inverse, the refined solve, eigsh and nnz_l after an update."""
     name, (src, fdt) = "g5-leaf1", DTYPES[0]
-    setup(monkeypatch, name)
-    n, s, _, _ = _system(name)
+    dense_setup(monkeypatch, name)
+    n, s, _, _ = dense_system(name)
     wu = _columns(name, 3, +1)
     s2 = s + wu @ wu.T
-    a2 = matrix(s2, src)
+    a2 = dense_matrix(s2, src)
     zref = np.linalg.inv(s2)
     eye = [np.ascontiguousarray(np.eye(n)[:, j]) for j in range(n)]
     with cholesky_nd(a2) as fresh:  # the selected inverse's own yardstick: the fresh factor's solves (x 8)
         xs = np.stack(cols_of(fresh.solve(Dense.from_columns(eye))), axis=1)
         yard = np.abs(np.diag(xs) - np.diag(zref)).max() / np.abs(zref).max()
-    with cholesky_nd(matrix(s, src)) as f:
+    with cholesky_nd(dense_matrix(s, src)) as f:
         f.l()
         assert f.nnz_l > 0
         f.update(w_csr(wu, src))
@@ -586,13 +523,13 @@ def test_everything_downstream_sees_the_new_factor(monkeypatch):
         assert f.nnz_l > 0
     # eigsh needs more than 25 unknowns for its Krylov space (test_gpu_nd_eig.py: ncv 60 at n = 121)
     name = "g11-leaf8"
-    setup(monkeypatch, name)
-    s = _system(name)[1]
+    dense_setup(monkeypatch, name)
+    s = dense_system(name)[1]
     wu = _columns(name, 3, +1)
     s2 = s + wu @ wu.T
-    with cholesky_nd(matrix(s, src)) as f:
+    with cholesky_nd(dense_matrix(s, src)) as f:
         f.update(w_csr(wu, src))
-        lam, _, einfo = f.eigsh(matrix(s2, src), 2, ncv=60)
+        lam, _, einfo = f.eigsh(dense_matrix(s2, src), 2, ncv=60)
         want = np.linalg.eigvalsh(s2)[:2]
         print("eigsh:", lam, want, einfo)
         assert einfo.converged.all()

@@ -15,6 +15,7 @@ import pytest
 from basic_sparse_matrix_amd import Csr, Dense, MatErr, MatErrKind, Panic, backward_substitution, \
     forward_substitution, solve
 from golden.golden_io import f32, matrix, scalars
+from nd_support import csr_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -94,13 +95,6 @@ def random_spd(rng, n, density, dtype):
     a = a + a.T
     a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
     return a.astype(dtype)
-
-
-def csr_arrays(dense):
-    nzr, nzc = np.nonzero(dense != 0)
-    counts = np.bincount(nzr, minlength=dense.shape[0])
-    rp = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), dense[nzr, nzc]
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

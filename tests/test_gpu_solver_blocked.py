@@ -11,16 +11,11 @@ import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, Panic, solve
 from golden.golden_io import matrix, scalars
+from nd_support import rel_err
 
 pytestmark = pytest.mark.gpu
 
 TOL = {np.float64: 1e-10, np.float32: 2e-3}
-
-
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
 
 
 def test_blocked_solve_golden(golden):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, Panic, solve
+from nd_support import csr_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -40,13 +41,6 @@ def assert_l_matches(got: Csr, rp, ci, v):
     assert np.array_equal(np.asarray(got.row_index, np.uint64), np.asarray(rp, np.uint64))
     assert np.array_equal(np.asarray(got.col_index, np.uint64), np.asarray(ci, np.uint64))
     assert same_bits(got.v, np.asarray(v, dtype=got.dtype))
-
-
-def csr_arrays(dense):
-    nzr, nzc = np.nonzero(dense != 0)
-    counts = np.bincount(nzr, minlength=dense.shape[0])
-    rp = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), dense[nzr, nzc]
 
 
 def random_sym(rng, n, density, dtype, diag):

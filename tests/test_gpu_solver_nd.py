@@ -13,23 +13,11 @@ import pytest
 
 from basic_sparse_matrix_amd import Csr, Dense, Panic, solve
 from golden.golden_io import matrix, scalars
+from nd_support import csr_arrays, rel_err
 
 pytestmark = pytest.mark.gpu
 
 TOL = {np.float64: 1e-10, np.float32: 2e-3}
-
-
-def rel_err(x, ref):
-    x = np.asarray(x, np.float64)
-    ref = np.asarray(ref, np.float64)
-    return np.linalg.norm(x - ref) / max(np.linalg.norm(ref), 1e-300)
-
-
-def csr_arrays(a):
-    nzr, nzc = np.nonzero(a != 0)
-    n = a.shape[0]
-    rp = np.concatenate([[0], np.cumsum(np.bincount(nzr, minlength=n))]).astype(np.uint64)
-    return rp, nzc.astype(np.uint64), a[nzr, nzc]
 
 
 def residual(rp, ci, v, x, b):

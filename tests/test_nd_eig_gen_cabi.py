@@ -12,18 +12,14 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import _lib
+from nd_support import assert_exported_and_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["bsm_nd_factor_eigsh_gen", "bsm_dev_nd_factor_eigsh_gen"]
 
 
 def test_eig_gen_symbols_exported_and_bound():
-    lib = _lib.load()
-    bound = {name for name, _, _ in _lib.SIGNATURES}
-    for n in NAMES:
-        assert hasattr(lib, n), f"{n} not exported by libbsm_hip.so"
-        assert n in bound, f"{n} not declared in _lib.SIGNATURES"
-    assert lib.bsm_api_version() == 1
+    assert_exported_and_bound(NAMES)
 
 
 def test_eig_gen_bad_arguments_need_no_device():

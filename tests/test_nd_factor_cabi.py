@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import _lib
+from nd_support import assert_exported_and_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["bsm_nd_factor_create", "bsm_nd_factor_solve", "bsm_nd_factor_info", "bsm_nd_factor_perm",
@@ -23,12 +24,7 @@ def _no_device():
 
 
 def test_factor_symbols_exported_and_bound():
-    lib = _lib.load()
-    bound = {name for name, _, _ in _lib.SIGNATURES}
-    for n in NAMES:
-        assert hasattr(lib, n), f"{n} not exported by libbsm_hip.so"
-        assert n in bound, f"{n} not declared in _lib.SIGNATURES"
-    assert lib.bsm_api_version() == 1
+    assert_exported_and_bound(NAMES)
 
 
 def test_factor_null_arguments_need_no_device():

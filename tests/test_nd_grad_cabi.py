@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import _lib
+from nd_support import assert_exported_and_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["bsm_dev_sddmm", "bsm_dev_nd_factor_sddmm", "bsm_dev_nd_factor_refactor_values",
@@ -21,12 +22,7 @@ F64, F32, I32 = (_lib.DTYPE_CODES[np.dtype(t)] for t in (np.float64, np.float32,
 
 
 def test_grad_symbols_exported_and_bound():
-    lib = _lib.load()
-    bound = {name for name, _, _ in _lib.SIGNATURES}
-    for n in NAMES:
-        assert hasattr(lib, n), f"{n} not exported by libbsm_hip.so"
-        assert n in bound, f"{n} not declared in _lib.SIGNATURES"
-    assert lib.bsm_api_version() == 1
+    assert_exported_and_bound(NAMES)
     assert (_lib.BSM_SDDMM_ALL, _lib.BSM_SDDMM_SYM_LOWER) == (0, 1)
 
 

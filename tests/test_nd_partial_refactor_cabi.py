@@ -13,18 +13,14 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import _lib
+from nd_support import assert_exported_and_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("bsm_nd_factor_refactor_partial", "bsm_nd_factor_refactor_since")
 
 
 def test_partial_refactor_symbols_exported_and_bound():
-    lib = _lib.load()
-    bound = {name for name, _, _ in _lib.SIGNATURES}
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} not exported by libbsm_hip.so"
-        assert name in bound
-    assert lib.bsm_api_version() == 1
+    assert_exported_and_bound(NAMES)
 
 
 def test_partial_refactor_argument_checks_need_no_device():

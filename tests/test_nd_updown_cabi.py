@@ -12,15 +12,13 @@ import numpy as np
 import pytest
 
 from basic_sparse_matrix_amd import _lib
+from nd_support import assert_exported_and_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_updown_symbol_exported_and_bound():
-    lib = _lib.load()
-    assert hasattr(lib, "bsm_nd_factor_updown"), "bsm_nd_factor_updown not exported by libbsm_hip.so"
-    assert "bsm_nd_factor_updown" in {name for name, _, _ in _lib.SIGNATURES}
-    assert lib.bsm_api_version() == 1
+    assert_exported_and_bound(["bsm_nd_factor_updown"])
 
 
 def test_updown_argument_checks_need_no_device():

@@ -7,6 +7,8 @@ own semantics where they coincide."""
 import numpy as np
 import pytest
 
+from nd_support import csr_arrays
+
 
 def random_spd(rng, n, density, dtype):
     a = np.zeros((n, n))
@@ -16,12 +18,6 @@ def random_spd(rng, n, density, dtype):
     a = a + a.T
     a[np.arange(n), np.arange(n)] = np.abs(a).sum(axis=1) + 1.0 + rng.random(n)
     return a.astype(dtype)
-
-
-def csr_arrays(dense):
-    nzr, nzc = np.nonzero(dense != 0)
-    counts = np.bincount(nzr, minlength=dense.shape[0])
-    return np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64), nzc.astype(np.uint64), dense[nzr, nzc]
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
