@@ -42,6 +42,7 @@
 #include <cstring>
 #include <vector>
 
+#include "addsub_plan.hpp"
 #include "bsm_internal.hpp"
 
 namespace bsm {
@@ -89,10 +90,8 @@ __device__ __forceinline__ void merge_range(int64_t ia, int64_t ea, int64_t ib, 
 }
 
 constexpr int64_t PIECE_CAP = 2048;  // entries per side staged in LDS by piece_merge
-constexpr int64_t LONG_ROW = 64;  // la + lb above this: cut the row into pieces (one thread's merge costs
-                                  // ~350 ns per step, dependent global loads: a 2,000-entry row took 55 + 108
-                                  // us of count + fill at e = 100k)
 
+// (LONG_ROW, addsub_plan.hpp: la + lb above it and the row is cut into pieces)
 __device__ __forceinline__ bool is_long(const int64_t* arp, const int64_t* brp, int64_t r) {
     return (arp[r + 1] - arp[r]) + (brp[r + 1] - brp[r]) > LONG_ROW;
 }
@@ -140,15 +139,8 @@ struct Piece {
 };
 
 // Long-row setup, chunk-parallel: a long row's two sides are cut into
-// chunks of LR_CHUNK entries (listed on the host from the rows' extents).
-constexpr int64_t LR_CHUNK = 2048;
-
-struct LrChunk {
-    int64_t l;     // long-row index
-    int64_t side;  // 0: self row, 1: rhs row
-    int64_t b, e;  // entry range
-    int64_t off;   // occurrences of M in the earlier chunks of the same row side
-};
+// chunks of LR_CHUNK entries (LrChunk, listed on the host from the rows'
+// extents: addsub_plan.hpp).
 
 // rank of `flag` within a 256-thread block, and the block total
 __device__ __forceinline__ int block_rank256(bool flag, int* wsum, int* total) {
@@ -1019,15 +1011,14 @@ struct CsrGuard {  // frees a half-built output on error paths
 
 // ---- add / sub, rows of moderate length: one wave per row -------------------
 // When no row has more than WROW_CAP entries on its two sides together (the
-// handles' analysed max row lengths say so, no device round trip), each row
+// handles' analysed max row lengths say so, no device round trip:
+// addsub_wave_rule, addsub_plan.hpp), each row
 // is one 64-lane workgroup: the wave stages the row's two sides in LDS
 // (coalesced), lane 0 runs the reference's two-pointer merge (merge_range,
 // sparse.rs:493-532) out of LDS and writes the kept outputs at the row's
 // upper-bound slot (arp[r] + brp[r]); a scan of the counts and a copy place
 // them. One host sync per call (the result's nnz), against the count / long
 // row / piece pipeline's five (§6b: the fixed cost of ss_add at e <= 200k).
-constexpr int WROW_CAP = 2048;
-
 template <typename T, bool SUB>
 __global__ __launch_bounds__(64) void addsub_wave(const int64_t* __restrict__ arp, const int32_t* __restrict__ acol,
                                                   const T* __restrict__ av, const int64_t* __restrict__ brp,
@@ -1107,265 +1098,293 @@ int addsub_wave_path(const bsm_csr* a, const bsm_csr* b, bool sub, bsm_csr** out
     return BSM_OK;
 }
 
-}  // namespace
+// ---- add / sub, the general path ---------------------------------------------
+// Its switches, one read site each (README.md lists them). Read on every call
+// (tests flip them within one process): BSM_SS_WAVE (sparse_addsub_dispatch)
+// and BSM_SS_DEBUG for its levels 1 (any value: the cut's lines), 2 and up
+// (piece_merge's stamps) and 4 (piece_split's stamps). Read once per process,
+// by the first call that gets there (another setting needs another process):
+// BSM_SS_SPLIT, BSM_SS_PRESPLIT, and whether BSM_SS_DEBUG is 3 (phase times).
+struct EnvInt {
+    bool set;
+    int value;  // 0 when unset
+};
+EnvInt env_int(const char* name) {
+    const char* e = getenv(name);
+    return {e != nullptr, e ? atoi(e) : 0};
+}
+EnvInt ss_debug() { return env_int("BSM_SS_DEBUG"); }
+bool ss_split() {  // BSM_SS_SPLIT=0: the round-2 wave-per-piece merge (piece_merge), for A/B
+    static const EnvInt e = env_int("BSM_SS_SPLIT");
+    return !e.set || e.value != 0;
+}
+// BSM_SS_PRESPLIT=1 (A/B; off by default, and under BSM_SS_DEBUG=4, whose
+// stamps are per top piece): a cuts-only pass first spreads every piece over
+// up to PRE_CUTS + 1 workgroups of the full pass. Within +-5 % of the single
+// pass at the benches' sizes (profiles/r03_s2h_*), so that stays the default.
+bool ss_presplit() {
+    static const EnvInt e = env_int("BSM_SS_PRESPLIT");
+    return e.set && e.value != 0;
+}
 
-int sparse_addsub_dispatch(const bsm_csr* a, const bsm_csr* b, bool sub, bsm_csr** out, hipStream_t s) {
-    BSM_REQUIRE(a && b && out, BSM_ERR_INVALID, "null argument");
-    BSM_REQUIRE(a->dtype == b->dtype, BSM_ERR_INVALID, "operands have different scalar types");
-    BSM_REQUIRE(a->rows == b->rows && a->cols == b->cols, BSM_ERR_DIMENSIONS, "IncorrectDimensions");
-    BSM_REQUIRE(a->rows > 0, BSM_ERR_PANIC,
-                "%s on a matrix with 0 rows: the reference's row loop never terminates (sparse.rs:%s)",
-                sub ? "sub_sparse" : "add_sparse", sub ? "593-596" : "533-537");
-    // every row short enough for one wave (the operands' analysed longest
-    // rows; a device-built operand not yet analysed takes the general path);
-    // BSM_SS_WAVE=0: the general path always (A/B)
-    const bool wave_ok = !getenv("BSM_SS_WAVE") || atoi(getenv("BSM_SS_WAVE")) != 0;
-    if (wave_ok && a->analysed && b->analysed && a->max_row_len + b->max_row_len <= (uint64_t)WROW_CAP &&
-        (a->nnz + b->nnz) * (sizeof(int32_t) + dtype_size(a->dtype)) <= (1ull << 30))
-        return addsub_wave_path(a, b, sub, out, s);
-    const uint64_t rows = a->rows;
-    DBuf cnt, lflag, lpos, ws;
-    CsrGuard g;
-    BSM_TRY(cnt.alloc(rows * sizeof(int32_t), s));
-    BSM_TRY(lflag.alloc(rows * sizeof(int32_t), s));
-    BSM_TRY(lpos.alloc((rows + 1) * sizeof(int64_t), s));
-    BSM_TRY(ws.alloc(scan_workspace_bytes(rows), s));
-    DBuf orp;
-    BSM_TRY(orp.alloc((rows + 1) * sizeof(int64_t), s));
-    // BSM_SS_DEBUG=3: host time per phase (each mark synchronises the stream)
-    static const bool tdbg = getenv("BSM_SS_DEBUG") && atoi(getenv("BSM_SS_DEBUG")) == 3;
-    auto t_last = host_now();
-    auto tmark = [&](const char* what) {
-        if (!tdbg) return;
+// The diagnostics. BSM_SS_DEBUG=3: host time per phase (each mark synchronises the stream)
+struct PhaseTimer {
+    hipStream_t s;
+    std::chrono::steady_clock::time_point t_last = host_now();
+    void mark(const char* what) {
+        static const bool on = ss_debug().value == 3;
+        if (!on) return;
         (void)hipStreamSynchronize(s);
         fprintf(stderr, "[bsm ss time] %-28s %8.3f ms\n", what, ms_since(t_last));
         t_last = host_now();
-    };
-    auto run = [&]<typename T, bool SUB>() -> int {
-        const T* av = static_cast<const T*>(a->vals);
-        const T* bv = static_cast<const T*>(b->vals);
+    }
+};
+
+// zeroed stamps for a kernel, per_piece of them for each piece, when a level asks for them; else d stays null
+int stamps_alloc(DBuf& d, bool on, int per_piece, int64_t n_pieces, hipStream_t s) {
+    if (!on) return BSM_OK;
+    BSM_TRY(d.alloc(per_piece * n_pieces * sizeof(unsigned long long), s));
+    BSM_HIP_TRY(hipMemsetAsync(d.p, 0, per_piece * n_pieces * sizeof(unsigned long long), s));
+    return BSM_OK;
+}
+
+// levels 2 and up: piece_merge's per-piece s_memtime stamps, where a merge step's cycles go (synchronises)
+int report_merge_stamps(const DBuf& pdbg, int64_t n_pieces, hipStream_t s) {
+    if (!pdbg.p) return BSM_OK;
+    std::vector<unsigned long long> h(6 * n_pieces);
+    BSM_HIP_TRY(hipMemcpyAsync(h.data(), pdbg.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    double sum[6] = {}, mx_len = 0, mx_cyc = 0;
+    for (int64_t p = 0; p < n_pieces; ++p) {
+        for (int k = 0; k < 6; ++k) sum[k] += (double)h[6 * p + k];
+        const double cyc = (double)(h[6 * p] + h[6 * p + 1] + h[6 * p + 4]);
+        if (cyc > mx_cyc) {
+            mx_cyc = cyc;
+            mx_len = (double)h[6 * p + 5];
+        }
+    }
+    fprintf(stderr, "[bsm ss debug] piece_merge over %lld pieces: per piece staging %.0f cycles, merge loop "
+            "%.0f (window refills %.0f) for %.0f steps = %.1f cycles/step, tail %.0f; longest piece %.0f "
+            "cycles over %.0f entries\n", (long long)n_pieces, sum[0] / n_pieces, sum[1] / n_pieces,
+            sum[2] / n_pieces, sum[3] / n_pieces, sum[3] > 0 ? sum[1] / sum[3] : 0.0, sum[4] / n_pieces,
+            mx_cyc, mx_len);
+    return BSM_OK;
+}
+
+// level 4: piece_split's per-piece stamps, their means and the slowest piece's (synchronises)
+int report_split_stamps(const DBuf& sdbg, int64_t n_pieces, hipStream_t s) {
+    if (!sdbg.p) return BSM_OK;
+    std::vector<unsigned long long> h(9 * n_pieces);
+    BSM_HIP_TRY(hipMemcpyAsync(h.data(), sdbg.p, h.size() * 8, hipMemcpyDeviceToHost, s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    int64_t worst = 0;
+    double sum[9] = {};
+    for (int64_t q = 0; q < n_pieces; ++q) {
+        for (int k = 0; k < 9; ++k) sum[k] += (double)h[9 * q + k];
+        if (h[9 * q] > h[9 * worst]) worst = q;
+    }
+    const unsigned long long* w = &h[9 * worst];
+    fprintf(stderr, "[bsm ss split] %lld pieces, mean %.0f cycles (cut %.0f, leaves %.0f, one-sided %.0f, "
+            "staging %.0f; scanned %.0f, flushes %.1f, leaves %.0f, size %.0f); longest: %llu cycles "
+            "(cut %llu, leaves %llu, one-sided %llu, staging %llu; scanned %llu, flushes %llu, leaves "
+            "%llu, size %llu)\n", (long long)n_pieces, sum[0] / n_pieces, sum[1] / n_pieces,
+            sum[2] / n_pieces, sum[3] / n_pieces, sum[4] / n_pieces, sum[5] / n_pieces,
+            sum[6] / n_pieces, sum[7] / n_pieces, sum[8] / n_pieces, w[0], w[1], w[2], w[3], w[4], w[5],
+            w[6], w[7], w[8]);
+    return BSM_OK;
+}
+
+// One call on the general path: its buffers, and its phases in the order run()
+// calls them. The object lives until the call's last synchronise (the end of
+// fill_output): a phase only queues work on these buffers, and hc and ps are
+// the host sources of queued H2D copies when there is no pinned staging.
+template <typename T, bool SUB>
+struct AddsubGeneral {
+    const bsm_csr *a, *b;
+    hipStream_t s;
+    PhaseTimer& tm;
+    const uint64_t rows = a->rows;
+    const T *av = static_cast<const T*>(a->vals), *bv = static_cast<const T*>(b->vals);
+    const int64_t n_slots = (int64_t)(a->nnz + b->nnz + 1);  // scratch positions of the long rows' outputs
+    const bool split = ss_split();
+    int64_t n_long = 0, n_chunks = 0, n_pieces = 0;
+    DBuf cnt, lflag, lpos, ws, orp;  // per row: kept outputs, long-row flag and its scan, scan workspace, row_ptr
+    DBuf long_rows, mval, pstart, pieces, pcnt, poff, first, ws2, tcol, tval;
+    DBuf scnt, srow, soff, ws3;  // the split path's used-position flags, long-row starts, offsets
+    DBuf ext, chunks, ccnt;
+    std::vector<int64_t> hx, hcnt, cnt_side, ps;  // extents; M occurrences per chunk, per row side; piece starts
+    std::vector<LrChunk> hc;
+    // the host-built chunk list and piece starts go up from pinned staging (a
+    // pageable copy behind running kernels can stall the host): three regions
+    // (at), all read before the call's last sync; no staging: from src itself
+    AddsubStaging at{};
+    char* pin = nullptr;
+    int h2d(void* dst, const void* src, size_t bytes, size_t off) {
+        if (!bytes) return BSM_OK;
+        if (pin) {
+            std::memcpy(pin + off, src, bytes);
+            BSM_HIP_TRY(hipMemcpyAsync(dst, pin + off, bytes, hipMemcpyHostToDevice, s));
+        } else {
+            BSM_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+        }
+        return BSM_OK;
+    }
+
+    // short rows: one thread's merge counts the kept outputs; long rows: flagged and counted
+    int count_short_rows() {
+        BSM_TRY(cnt.alloc(rows * sizeof(int32_t), s));
+        BSM_TRY(lflag.alloc(rows * sizeof(int32_t), s));
+        BSM_TRY(lpos.alloc((rows + 1) * sizeof(int64_t), s));
+        BSM_TRY(ws.alloc(scan_workspace_bytes(rows), s));
+        BSM_TRY(orp.alloc((rows + 1) * sizeof(int64_t), s));
         addsub_count<T, SUB><<<grid_of(rows), 256, 0, s>>>((int64_t)rows, a->row_ptr, a->col, av, b->row_ptr, b->col,
                                                            bv, cnt.as<int32_t>(), lflag.as<int32_t>());
         BSM_HIP_TRY(hipGetLastError());
-        // long rows: list, pieces, piece counts
         BSM_TRY(exclusive_scan_i32_to_i64(lflag.as<int32_t>(), lpos.as<int64_t>(), rows, ws.p, ws.bytes, s));
-        int64_t n_long = 0;
         BSM_HIP_TRY(read_dev(&n_long, lpos.as<int64_t>() + rows, sizeof(int64_t), s));
         BSM_HIP_TRY(hipStreamSynchronize(s));
-        tmark("count + long-row scan");
-        DBuf long_rows, mval, pstart, pieces, pcnt, poff, first, ws2, tcol, tval;
-        DBuf scnt, srow, soff, ws3;  // the split path's used-position flags, long-row starts, offsets
-        // host inputs of queued H2D copies: alive until the call's last sync
-        std::vector<LrChunk> hc;
-        std::vector<int64_t> ps;
-        // BSM_SS_SPLIT=0: the round-2 wave-per-piece merge (piece_merge), for A/B
-        static const bool split = !getenv("BSM_SS_SPLIT") || atoi(getenv("BSM_SS_SPLIT")) != 0;
-        const int64_t n_slots = (int64_t)(a->nnz + b->nnz + 1);
-        int64_t n_pieces = 0;
-        if (n_long) {
-            BSM_TRY(long_rows.alloc(n_long * sizeof(int64_t), s));
-            BSM_TRY(mval.alloc(n_long * sizeof(int32_t), s));
-            BSM_TRY(pstart.alloc((n_long + 1) * sizeof(int64_t), s));
-            DBuf ext;
-            BSM_TRY(ext.alloc(4 * n_long * sizeof(int64_t), s));
-            compact_flags<<<grid_of(rows), 256, 0, s>>>((int64_t)rows, lflag.as<int32_t>(), lpos.as<int64_t>(),
-                                                        long_rows.as<int64_t>());
-            long_extents<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), a->row_ptr, b->row_ptr,
-                                                         ext.as<int64_t>());
-            BSM_HIP_TRY(hipGetLastError());
-            std::vector<int64_t> hx(4 * n_long);
-            BSM_HIP_TRY(hipMemcpyAsync(hx.data(), ext.p, hx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            BSM_HIP_TRY(hipStreamSynchronize(s));
-        tmark("long rows + extents");
-            for (int64_t l = 0; l < n_long; ++l)
-                for (int64_t side = 0; side < 2; ++side)
-                    for (int64_t b0 = hx[4 * l + 2 * side]; b0 < hx[4 * l + 2 * side + 1]; b0 += LR_CHUNK)
-                        hc.push_back({l, side, b0, std::min(b0 + LR_CHUNK, hx[4 * l + 2 * side + 1]), 0});
-            const int64_t n_chunks = (int64_t)hc.size();
-            // the host-built chunk list and piece starts go up from pinned
-            // staging (a pageable copy behind running kernels can stall the
-            // host); three regions, all read before the call's last sync
-            const size_t hc_b = (size_t)n_chunks * sizeof(LrChunk), ps_b = (size_t)(n_long + 1) * sizeof(int64_t);
-            const size_t hc_al = (hc_b + 255) & ~size_t(255);
-            char* pin = static_cast<char*>(pinned(2 * hc_al + ps_b));
-            auto h2d = [&](void* dst, const void* src, size_t bytes, size_t off) -> int {
-                if (!bytes) return BSM_OK;
-                if (pin) {
-                    std::memcpy(pin + off, src, bytes);
-                    BSM_HIP_TRY(hipMemcpyAsync(dst, pin + off, bytes, hipMemcpyHostToDevice, s));
-                } else {
-                    BSM_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-                }
-                return BSM_OK;
-            };
-            DBuf chunks, ccnt;
-            BSM_TRY(chunks.alloc((n_chunks ? n_chunks : 1) * sizeof(LrChunk), s));
-            BSM_TRY(ccnt.alloc((n_chunks ? n_chunks : 1) * sizeof(int64_t), s));
-            BSM_HIP_TRY(hipMemsetAsync(mval.p, 0xff, n_long * sizeof(int32_t), s));  // -1
-            std::vector<int64_t> hcnt(n_chunks);
-            if (n_chunks) {
-                BSM_TRY(h2d(chunks.p, hc.data(), hc_b, 0));
-                chunk_reduce<true><<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col,
-                                                                      mval.as<int32_t>(), nullptr);
-                chunk_reduce<false><<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col,
-                                                                       mval.as<int32_t>(), ccnt.as<int64_t>());
-                BSM_HIP_TRY(hipGetLastError());
-                BSM_HIP_TRY(hipMemcpyAsync(hcnt.data(), ccnt.p, n_chunks * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-                BSM_HIP_TRY(hipStreamSynchronize(s));  // hc (host) is read by the copy above
-            }
-        tmark("row maxima + counts");
-            // M pairs per row: min of the two sides' counts; chunk offsets
-            std::vector<int64_t> cnt_side(2 * n_long, 0);
-            ps.assign(n_long + 1, 0);
-            for (int64_t i = 0; i < n_chunks; ++i) {
-                hc[i].off = cnt_side[2 * hc[i].l + hc[i].side];
-                cnt_side[2 * hc[i].l + hc[i].side] += hcnt[i];
-            }
-            for (int64_t l = 0; l < n_long; ++l) ps[l + 1] = ps[l] + std::min(cnt_side[2 * l], cnt_side[2 * l + 1]) + 1;
-            n_pieces = ps[n_long];
-            if (getenv("BSM_SS_DEBUG")) {  // the long rows' cut: M occurrences per side and the pieces
-                for (int64_t l = 0; l < n_long && l < 4; ++l)
-                    fprintf(stderr, "[bsm ss debug] long row %lld: extents a %lld b %lld, M count a %lld b %lld\n",
-                            (long long)l, (long long)(hx[4 * l + 1] - hx[4 * l]), (long long)(hx[4 * l + 3] - hx[4 * l + 2]),
-                            (long long)cnt_side[2 * l], (long long)cnt_side[2 * l + 1]);
-                fprintf(stderr, "[bsm ss debug] long rows %lld, chunks %lld, pieces %lld\n", (long long)n_long,
-                        (long long)n_chunks, (long long)n_pieces);
-            }
-            BSM_TRY(h2d(pstart.p, ps.data(), ps_b, 2 * hc_al));
-            BSM_TRY(pieces.alloc(n_pieces * sizeof(Piece), s));
-            BSM_TRY(pcnt.alloc(n_pieces * sizeof(int32_t), s));
-            BSM_TRY(poff.alloc((n_pieces + 1) * sizeof(int64_t), s));
-            BSM_TRY(first.alloc(n_pieces * sizeof(int64_t), s));
-            BSM_TRY(ws2.alloc(scan_workspace_bytes(n_pieces), s));
-            long_piece_init<<<(unsigned)n_long, 256, 0, s>>>(n_long, long_rows.as<int64_t>(), ext.as<int64_t>(),
-                                                             pstart.as<int64_t>(), pieces.as<Piece>(),
-                                                             first.as<int64_t>());
-            if (n_chunks) {
-                BSM_TRY(h2d(chunks.p, hc.data(), hc_b, hc_al));
-                chunk_pieces<<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col, mval.as<int32_t>(),
-                                                                pstart.as<int64_t>(), pieces.as<Piece>());
-            }
-            BSM_HIP_TRY(hipGetLastError());
-        tmark("pieces");
-            BSM_TRY(tcol.alloc((a->nnz + b->nnz + 1) * sizeof(int32_t), s));
-            BSM_TRY(tval.alloc((a->nnz + b->nnz + 1) * sizeof(T), s));
-            BSM_REQUIRE(n_pieces < (1ll << 31), BSM_ERR_UNSUPPORTED, "too many pieces");
-            if (split) {  // recursive cut, one lane per leaf; outputs placed by a scan of the slot counts
-                BSM_TRY(scnt.alloc(n_slots * sizeof(int32_t), s));
-                BSM_TRY(srow.alloc(n_long * sizeof(int64_t), s));  // the long rows' first positions
-                BSM_TRY(soff.alloc((n_slots + 1) * sizeof(int64_t), s));
-                BSM_TRY(ws3.alloc(scan_workspace_bytes((uint64_t)n_slots), s));
-                BSM_HIP_TRY(hipMemsetAsync(tcol.p, 0xff, n_slots * sizeof(int32_t), s));  // -1: unused
-                const char* ssd4 = getenv("BSM_SS_DEBUG");
-                DBuf sdbg;
-                if (ssd4 && atoi(ssd4) == 4) {
-                    BSM_TRY(sdbg.alloc(9 * n_pieces * sizeof(unsigned long long), s));
-                    BSM_HIP_TRY(hipMemsetAsync(sdbg.p, 0, 9 * n_pieces * sizeof(unsigned long long), s));
-                }
-                const size_t split_lds = 2 * split_cap<T>() * (sizeof(int32_t) + sizeof(T));
-                // BSM_SS_PRESPLIT=1 (A/B; off by default, and under BSM_SS_DEBUG=4,
-                // whose stamps are per top piece): a cuts-only pass first spreads
-                // every piece over up to PRE_CUTS + 1 workgroups of the full pass.
-                // Within +-5 % of the single pass at the benches' sizes
-                // (profiles/r03_s2h_*), so the single pass stays the default.
-                static const bool presplit = getenv("BSM_SS_PRESPLIT") && atoi(getenv("BSM_SS_PRESPLIT")) != 0;
-                if (presplit && !sdbg.p && (uint64_t)n_pieces * (PRE_CUTS + 1) < (1ull << 31)) {
-                    const int64_t n2 = n_pieces * (PRE_CUTS + 1);
-                    DBuf pieces2, cnt2;
-                    BSM_TRY(pieces2.alloc(n2 * sizeof(Piece), s));
-                    BSM_TRY(cnt2.alloc(sizeof(unsigned), s));
-                    BSM_HIP_TRY(hipMemsetAsync(cnt2.p, 0, sizeof(unsigned), s));
-                    piece_split<T, SUB, true><<<(unsigned)n_pieces, 64, split_lds, s>>>(
-                        pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), nullptr, nullptr,
-                        pieces2.as<Piece>(), cnt2.as<unsigned>());
-                    piece_split<T, SUB><<<(unsigned)n2, 64, split_lds, s>>>(
-                        pieces2.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), nullptr,
-                        cnt2.as<unsigned>());
-                } else {
-                    piece_split<T, SUB><<<(unsigned)n_pieces, 64, split_lds, s>>>(
-                        pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(),
-                        sdbg.as<unsigned long long>());
-                }
-                pos_flags<<<grid_of((uint64_t)n_slots), 256, 0, s>>>(n_slots, tcol.as<int32_t>(), scnt.as<int32_t>());
-                if (sdbg.p) {
-                    std::vector<unsigned long long> h(9 * n_pieces);
-                    BSM_HIP_TRY(hipMemcpyAsync(h.data(), sdbg.p, h.size() * 8, hipMemcpyDeviceToHost, s));
-                    BSM_HIP_TRY(hipStreamSynchronize(s));
-                    int64_t worst = 0;
-                    double sum[9] = {};
-                    for (int64_t q = 0; q < n_pieces; ++q) {
-                        for (int k = 0; k < 9; ++k) sum[k] += (double)h[9 * q + k];
-                        if (h[9 * q] > h[9 * worst]) worst = q;
-                    }
-                    const unsigned long long* w = &h[9 * worst];
-                    fprintf(stderr, "[bsm ss split] %lld pieces, mean %.0f cycles (cut %.0f, leaves %.0f, one-sided %.0f, "
-                            "staging %.0f; scanned %.0f, flushes %.1f, leaves %.0f, size %.0f); longest: %llu cycles "
-                            "(cut %llu, leaves %llu, one-sided %llu, staging %llu; scanned %llu, flushes %llu, leaves "
-                            "%llu, size %llu)\n", (long long)n_pieces, sum[0] / n_pieces, sum[1] / n_pieces,
-                            sum[2] / n_pieces, sum[3] / n_pieces, sum[4] / n_pieces, sum[5] / n_pieces,
-                            sum[6] / n_pieces, sum[7] / n_pieces, sum[8] / n_pieces, w[0], w[1], w[2], w[3], w[4], w[5],
-                            w[6], w[7], w[8]);
-                }
-                // (scnt: 1 at every used scratch position, srow: its row)
-                BSM_HIP_TRY(hipGetLastError());
-                BSM_TRY(exclusive_scan_i32_to_i64(scnt.as<int32_t>(), soff.as<int64_t>(), (uint64_t)n_slots, ws3.p,
-                                                  ws3.bytes, s));
-                long_row_totals_slots<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), a->row_ptr,
-                                                                       b->row_ptr, soff.as<int64_t>(), cnt.as<int32_t>(),
-                                                                       srow.as<int64_t>());
-                BSM_HIP_TRY(hipGetLastError());
-        tmark("piece_split + scan");
-            } else {
-            const char* ssd = getenv("BSM_SS_DEBUG");
-            DBuf pdbg;
-            if (ssd && atoi(ssd) >= 2) {
-                BSM_TRY(pdbg.alloc(6 * n_pieces * sizeof(unsigned long long), s));
-                BSM_HIP_TRY(hipMemsetAsync(pdbg.p, 0, 6 * n_pieces * sizeof(unsigned long long), s));
-            }
-            piece_merge<T, SUB><<<(unsigned)n_pieces, 64, 2 * PIECE_CAP * (sizeof(int32_t) + sizeof(T)), s>>>(
-                pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), pcnt.as<int32_t>(),
-                pdbg.as<unsigned long long>());
-            BSM_HIP_TRY(hipGetLastError());
-            if (pdbg.p) {  // per-piece s_memtime stamps: where a merge step's cycles go
-                std::vector<unsigned long long> h(6 * n_pieces);
-                BSM_HIP_TRY(hipMemcpyAsync(h.data(), pdbg.p, h.size() * sizeof(unsigned long long),
-                                           hipMemcpyDeviceToHost, s));
-                BSM_HIP_TRY(hipStreamSynchronize(s));
-                double sum[6] = {}, mx_len = 0, mx_cyc = 0;
-                for (int64_t p = 0; p < n_pieces; ++p) {
-                    for (int k = 0; k < 6; ++k) sum[k] += (double)h[6 * p + k];
-                    const double cyc = (double)(h[6 * p] + h[6 * p + 1] + h[6 * p + 4]);
-                    if (cyc > mx_cyc) {
-                        mx_cyc = cyc;
-                        mx_len = (double)h[6 * p + 5];
-                    }
-                }
-                fprintf(stderr, "[bsm ss debug] piece_merge over %lld pieces: per piece staging %.0f cycles, merge loop "
-                        "%.0f (window refills %.0f) for %.0f steps = %.1f cycles/step, tail %.0f; longest piece %.0f "
-                        "cycles over %.0f entries\n", (long long)n_pieces, sum[0] / n_pieces, sum[1] / n_pieces,
-                        sum[2] / n_pieces, sum[3] / n_pieces, sum[3] > 0 ? sum[1] / sum[3] : 0.0, sum[4] / n_pieces,
-                        mx_cyc, mx_len);
-            }
-            BSM_TRY(exclusive_scan_i32_to_i64(pcnt.as<int32_t>(), poff.as<int64_t>(), n_pieces, ws2.p, ws2.bytes, s));
-            long_row_totals<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), pstart.as<int64_t>(),
-                                                             poff.as<int64_t>(), cnt.as<int32_t>());
-            BSM_HIP_TRY(hipGetLastError());
-            }
+        return BSM_OK;
+    }
+
+    // the long rows' list, and their extents on the host
+    int long_rows_list() {
+        BSM_TRY(long_rows.alloc(n_long * sizeof(int64_t), s));
+        BSM_TRY(mval.alloc(n_long * sizeof(int32_t), s));
+        BSM_TRY(pstart.alloc((n_long + 1) * sizeof(int64_t), s));
+        BSM_TRY(ext.alloc(4 * n_long * sizeof(int64_t), s));
+        compact_flags<<<grid_of(rows), 256, 0, s>>>((int64_t)rows, lflag.as<int32_t>(), lpos.as<int64_t>(),
+                                                    long_rows.as<int64_t>());
+        long_extents<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), a->row_ptr, b->row_ptr,
+                                                     ext.as<int64_t>());
+        BSM_HIP_TRY(hipGetLastError());
+        hx.resize(4 * n_long);
+        BSM_HIP_TRY(hipMemcpyAsync(hx.data(), ext.p, hx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        BSM_HIP_TRY(hipStreamSynchronize(s));
+        return BSM_OK;
+    }
+
+    // the chunk list; every long row's largest column M, then M's occurrences per chunk on the host
+    int long_rows_counts() {
+        hc = addsub_chunk_list(n_long, hx.data());
+        n_chunks = (int64_t)hc.size();
+        at = addsub_staging((size_t)n_chunks * sizeof(LrChunk), (size_t)(n_long + 1) * sizeof(int64_t));
+        pin = static_cast<char*>(pinned(at.total));
+        BSM_TRY(chunks.alloc((n_chunks ? n_chunks : 1) * sizeof(LrChunk), s));
+        BSM_TRY(ccnt.alloc((n_chunks ? n_chunks : 1) * sizeof(int64_t), s));
+        BSM_HIP_TRY(hipMemsetAsync(mval.p, 0xff, n_long * sizeof(int32_t), s));  // -1
+        hcnt.resize(n_chunks);
+        if (!n_chunks) return BSM_OK;
+        BSM_TRY(h2d(chunks.p, hc.data(), n_chunks * sizeof(LrChunk), at.chunks));
+        chunk_reduce<true><<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col,
+                                                              mval.as<int32_t>(), nullptr);
+        chunk_reduce<false><<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col,
+                                                               mval.as<int32_t>(), ccnt.as<int64_t>());
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_HIP_TRY(hipMemcpyAsync(hcnt.data(), ccnt.p, n_chunks * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        BSM_HIP_TRY(hipStreamSynchronize(s));  // hc (host) is read by the copy above
+        return BSM_OK;
+    }
+
+    // the cut: the M pairs of a row (the min of its two sides' counts) close its pieces
+    int long_rows_pieces() {
+        n_pieces = addsub_piece_plan(n_long, hc, hcnt, cnt_side, ps);
+        if (ss_debug().set) {  // any value: the long rows' cut, M occurrences per side and the pieces
+            for (int64_t l = 0; l < n_long && l < 4; ++l)
+                fprintf(stderr, "[bsm ss debug] long row %lld: extents a %lld b %lld, M count a %lld b %lld\n",
+                        (long long)l, (long long)(hx[4 * l + 1] - hx[4 * l]), (long long)(hx[4 * l + 3] - hx[4 * l + 2]),
+                        (long long)cnt_side[2 * l], (long long)cnt_side[2 * l + 1]);
+            fprintf(stderr, "[bsm ss debug] long rows %lld, chunks %lld, pieces %lld\n", (long long)n_long,
+                    (long long)n_chunks, (long long)n_pieces);
         }
+        BSM_TRY(h2d(pstart.p, ps.data(), ps.size() * sizeof(int64_t), at.pstart));
+        BSM_TRY(pieces.alloc(n_pieces * sizeof(Piece), s));
+        BSM_TRY(pcnt.alloc(n_pieces * sizeof(int32_t), s));
+        BSM_TRY(poff.alloc((n_pieces + 1) * sizeof(int64_t), s));
+        BSM_TRY(first.alloc(n_pieces * sizeof(int64_t), s));
+        BSM_TRY(ws2.alloc(scan_workspace_bytes(n_pieces), s));
+        long_piece_init<<<(unsigned)n_long, 256, 0, s>>>(n_long, long_rows.as<int64_t>(), ext.as<int64_t>(),
+                                                         pstart.as<int64_t>(), pieces.as<Piece>(),
+                                                         first.as<int64_t>());
+        if (n_chunks) {
+            BSM_TRY(h2d(chunks.p, hc.data(), n_chunks * sizeof(LrChunk), at.chunks_off));
+            chunk_pieces<<<(unsigned)n_chunks, 256, 0, s>>>(chunks.as<LrChunk>(), a->col, b->col, mval.as<int32_t>(),
+                                                            pstart.as<int64_t>(), pieces.as<Piece>());
+        }
+        BSM_HIP_TRY(hipGetLastError());
+        return BSM_OK;
+    }
+
+    // piece_split: recursive cut, one lane per leaf; outputs placed by a scan of the slot counts
+    // (scnt: 1 at every used scratch position, srow: the long rows' first positions)
+    int merge_by_piece_split() {
+        BSM_TRY(scnt.alloc(n_slots * sizeof(int32_t), s));
+        BSM_TRY(srow.alloc(n_long * sizeof(int64_t), s));
+        BSM_TRY(soff.alloc((n_slots + 1) * sizeof(int64_t), s));
+        BSM_TRY(ws3.alloc(scan_workspace_bytes((uint64_t)n_slots), s));
+        BSM_HIP_TRY(hipMemsetAsync(tcol.p, 0xff, n_slots * sizeof(int32_t), s));  // -1: unused
+        DBuf sdbg;
+        BSM_TRY(stamps_alloc(sdbg, ss_debug().value == 4, 9, n_pieces, s));
+        const size_t split_lds = 2 * split_cap<T>() * (sizeof(int32_t) + sizeof(T));
+        if (ss_presplit() && !sdbg.p && addsub_presplit_fits(n_pieces, PRE_CUTS)) {
+            const int64_t n2 = n_pieces * (PRE_CUTS + 1);
+            DBuf pieces2, cnt2;
+            BSM_TRY(pieces2.alloc(n2 * sizeof(Piece), s));
+            BSM_TRY(cnt2.alloc(sizeof(unsigned), s));
+            BSM_HIP_TRY(hipMemsetAsync(cnt2.p, 0, sizeof(unsigned), s));
+            piece_split<T, SUB, true><<<(unsigned)n_pieces, 64, split_lds, s>>>(
+                pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), nullptr, nullptr,
+                pieces2.as<Piece>(), cnt2.as<unsigned>());
+            piece_split<T, SUB><<<(unsigned)n2, 64, split_lds, s>>>(
+                pieces2.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), nullptr,
+                cnt2.as<unsigned>());
+        } else {
+            piece_split<T, SUB><<<(unsigned)n_pieces, 64, split_lds, s>>>(
+                pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(),
+                sdbg.as<unsigned long long>());
+        }
+        pos_flags<<<grid_of((uint64_t)n_slots), 256, 0, s>>>(n_slots, tcol.as<int32_t>(), scnt.as<int32_t>());
+        BSM_TRY(report_split_stamps(sdbg, n_pieces, s));
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_TRY(exclusive_scan_i32_to_i64(scnt.as<int32_t>(), soff.as<int64_t>(), (uint64_t)n_slots, ws3.p, ws3.bytes,
+                                          s));
+        long_row_totals_slots<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), a->row_ptr, b->row_ptr,
+                                                               soff.as<int64_t>(), cnt.as<int32_t>(),
+                                                               srow.as<int64_t>());
+        BSM_HIP_TRY(hipGetLastError());
+        return BSM_OK;
+    }
+
+    // piece_merge (BSM_SS_SPLIT=0): one wave per piece; outputs placed by a scan of the pieces' counts
+    int merge_by_piece_merge() {
+        DBuf pdbg;
+        BSM_TRY(stamps_alloc(pdbg, ss_debug().value >= 2, 6, n_pieces, s));
+        piece_merge<T, SUB><<<(unsigned)n_pieces, 64, 2 * PIECE_CAP * (sizeof(int32_t) + sizeof(T)), s>>>(
+            pieces.as<Piece>(), a->col, av, b->col, bv, tcol.as<int32_t>(), tval.as<T>(), pcnt.as<int32_t>(),
+            pdbg.as<unsigned long long>());
+        BSM_HIP_TRY(hipGetLastError());
+        BSM_TRY(report_merge_stamps(pdbg, n_pieces, s));
+        BSM_TRY(exclusive_scan_i32_to_i64(pcnt.as<int32_t>(), poff.as<int64_t>(), n_pieces, ws2.p, ws2.bytes, s));
+        long_row_totals<<<grid_of(n_long), 256, 0, s>>>(n_long, long_rows.as<int64_t>(), pstart.as<int64_t>(),
+                                                         poff.as<int64_t>(), cnt.as<int32_t>());
+        BSM_HIP_TRY(hipGetLastError());
+        return BSM_OK;
+    }
+
+    // row_ptr by a scan of the rows' counts, the output, the short rows' fill, the long rows' results copied in
+    int fill_output(CsrGuard& g) {
         BSM_TRY(exclusive_scan_i32_to_i64(cnt.as<int32_t>(), orp.as<int64_t>(), rows, ws.p, ws.bytes, s));
         int64_t nnz = 0;
         // the output holds at most nnz(a) + nnz(b) entries: allocated at that
         // bound (when it is small) the fill is queued behind the scan and the
         // count is read with the call's last sync; else the count first
-        const uint64_t nnz_ub = a->nnz + b->nnz;
-        const bool ub = nnz_ub * (sizeof(int32_t) + sizeof(T)) <= (1ull << 30);
+        const bool ub = addsub_out_at_bound(a->nnz, b->nnz, sizeof(T));
         if (!ub) {
             BSM_HIP_TRY(read_dev(&nnz, orp.as<int64_t>() + rows, sizeof(int64_t), s));
             BSM_HIP_TRY(hipStreamSynchronize(s));
         }
-        tmark("row scan + nnz");
-        BSM_TRY(csr_alloc(&g.m, a->dtype, rows, a->cols, ub ? nnz_ub : (uint64_t)nnz));
-        tmark("output alloc");
+        tm.mark("row scan + nnz");
+        BSM_TRY(csr_alloc(&g.m, a->dtype, rows, a->cols, ub ? a->nnz + b->nnz : (uint64_t)nnz));
+        tm.mark("output alloc");
         BSM_HIP_TRY(hipMemcpyAsync(g.m->row_ptr, orp.p, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
         addsub_fill<T, SUB><<<grid_of(rows), 256, 0, s>>>((int64_t)rows, a->row_ptr, a->col, av, b->row_ptr, b->col,
                                                           bv, orp.as<int64_t>(), g.m->col, static_cast<T*>(g.m->vals));
@@ -1385,18 +1404,62 @@ int sparse_addsub_dispatch(const bsm_csr* a, const bsm_csr* b, bool sub, bsm_csr
             BSM_HIP_TRY(read_dev(&nnz, orp.as<int64_t>() + rows, sizeof(int64_t), s));  // syncs the stream
             g.m->nnz = (uint64_t)nnz;
         }
-        BSM_HIP_TRY(hipStreamSynchronize(s));  // the piece buffers die with this scope
-        tmark("fill + copy");
+        BSM_HIP_TRY(hipStreamSynchronize(s));  // the call's last: the buffers may go
+        tm.mark("fill + copy");
         return BSM_OK;
-    };
-    BSM_TRY(dispatch_dtype(a->dtype, [&]<typename T>() -> int {
-        return sub ? run.template operator()<T, true>() : run.template operator()<T, false>();
-    }));
-    tmark("scope exit (frees)");
+    }
+
+    int run(CsrGuard& g) {
+        BSM_TRY(count_short_rows());
+        tm.mark("count + long-row scan");
+        if (n_long) {
+            BSM_TRY(long_rows_list());
+            tm.mark("long rows + extents");
+            BSM_TRY(long_rows_counts());
+            tm.mark("row maxima + counts");
+            BSM_TRY(long_rows_pieces());
+            tm.mark("pieces");
+            BSM_TRY(tcol.alloc((a->nnz + b->nnz + 1) * sizeof(int32_t), s));
+            BSM_TRY(tval.alloc((a->nnz + b->nnz + 1) * sizeof(T), s));
+            BSM_REQUIRE(addsub_pieces_fit(n_pieces), BSM_ERR_UNSUPPORTED, "too many pieces");
+            BSM_TRY(split ? merge_by_piece_split() : merge_by_piece_merge());
+            if (split) tm.mark("piece_split + scan");
+        }
+        return fill_output(g);
+    }
+};
+
+template <typename T, bool SUB>
+int addsub_general_path(const bsm_csr* a, const bsm_csr* b, bsm_csr** out, hipStream_t s) {
+    PhaseTimer tm{s};
+    CsrGuard g;
+    BSM_TRY((AddsubGeneral<T, SUB>{a, b, s, tm}.run(g)));
+    tm.mark("scope exit (frees)");
     // no eager csr_analyse: the result's columns come from the operands (in
     // bounds); its row order and longest row are found when first needed
     *out = g.release();
     return BSM_OK;
+}
+
+}  // namespace
+
+int sparse_addsub_dispatch(const bsm_csr* a, const bsm_csr* b, bool sub, bsm_csr** out, hipStream_t s) {
+    BSM_REQUIRE(a && b && out, BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(a->dtype == b->dtype, BSM_ERR_INVALID, "operands have different scalar types");
+    BSM_REQUIRE(a->rows == b->rows && a->cols == b->cols, BSM_ERR_DIMENSIONS, "IncorrectDimensions");
+    BSM_REQUIRE(a->rows > 0, BSM_ERR_PANIC,
+                "%s on a matrix with 0 rows: the reference's row loop never terminates (sparse.rs:%s)",
+                sub ? "sub_sparse" : "add_sparse", sub ? "593-596" : "533-537");
+    // every row short enough for one wave (the operands' analysed longest
+    // rows; a device-built operand not yet analysed takes the general path);
+    // BSM_SS_WAVE=0: the general path always (A/B)
+    const EnvInt wave = env_int("BSM_SS_WAVE");
+    if (addsub_wave_rule(wave.set, wave.value, a->analysed, b->analysed, a->max_row_len, b->max_row_len, a->nnz,
+                         b->nnz, dtype_size(a->dtype)))
+        return addsub_wave_path(a, b, sub, out, s);
+    return dispatch_dtype(a->dtype, [&]<typename T>() -> int {
+        return sub ? addsub_general_path<T, true>(a, b, out, s) : addsub_general_path<T, false>(a, b, out, s);
+    });
 }
 
 int sparse_mul_dispatch(const bsm_csr* a, const bsm_csr* b, bsm_csr** out, hipStream_t s) {

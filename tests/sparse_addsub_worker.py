@@ -25,6 +25,9 @@ case names (dt: f64 f32 i32 u32 i64):
   many:<dt>               600 rows, 400 of them long, of every kind
   pre:<dt>                pieces of 512 / 513 entries (PRE_MIN) and one nested
                           piece that takes all PRE_CUTS cuts of the first pass
+  diag:<kind>:<dt>        the smallest long-row operands (the diagnostic
+                          levels); kind: row65 (one row of LONG_ROW + 1
+                          entries) | cap1 (split_cap<T>() + 1 per side)
 """
 
 import json
@@ -38,7 +41,7 @@ if ROOT not in sys.path:
 
 import numpy as np  # noqa: E402
 
-# the constants of csrc/kernels_sparse.hip
+# the constants of csrc/addsub_plan.hpp (the first three) and csrc/kernels_sparse.hip
 WROW_CAP = 2048
 LONG_ROW = 64
 LR_CHUNK = 2048
@@ -344,8 +347,23 @@ def build_pre(dtype):
     return assemble(rng, [pa, short, na], [pb, short[:2], nb], cols, dtype)
 
 
+# ------------------------------------------------------------ section 8 ----
+def build_diag(kind, dtype):
+    """The smallest long-row operands, for the diagnostic levels: row65, one
+    long row of LONG_ROW + 1 entries (33 and 32) between two short rows;
+    cap1, one row of split_cap<T>() + 1 entries on each side."""
+    rng = np.random.default_rng(67)
+    la, lb = (33, 32) if kind == "row65" else (split_cap(dtype) + 1,) * 2
+    cols = 40 if kind == "row65" else 900
+    ra = [rng.integers(0, cols, n) for n in (5, la, 7)]
+    rb = [rng.integers(0, cols, n) for n in (3, lb, 0)]
+    return assemble(rng, ra, rb, cols, dtype)
+
+
 def build(name):
     p = name.split(":")
+    if p[0] == "diag":
+        return build_diag(p[1], DTYPES[p[2]])
     if p[0] == "long":
         return build_long(p[1], DTYPES[p[2]])
     if p[0] == "caps":

@@ -5,7 +5,9 @@ pipeline (chunks, the cut at the pairs of the row maximum, piece_split's
 staging caps, work stack, leaf list, scan budget, median cut and one-sided
 copy) at every scalar width; the older piece_merge (BSM_SS_SPLIT=0) and the
 two-pass form (BSM_SS_PRESPLIT=1), which are read once per process, in child
-processes (tests/sparse_addsub_worker.py, which also builds the operands).
+processes (tests/sparse_addsub_worker.py, which also builds the operands);
+and the diagnostic levels 2, 3 and 4 of BSM_SS_DEBUG, which hand the kernels
+their stamp buffers or end every phase with a synchronise.
 
 Every comparison is add and sub in both operand orders. Where a test means a
 path it also reads the library's BSM_SS_DEBUG line ("long rows, chunks,
@@ -43,24 +45,27 @@ def n_long_rows(sa, sb):
     return int(np.count_nonzero(la + lb > W.LONG_ROW))
 
 
-def check(orc, capfd, monkeypatch, case, pipeline=True, cmp=assert_csr_bits):
+def check(orc, capfd, monkeypatch, case, pipeline=True, cmp=assert_csr_bits, debug="1"):
     """add and sub in both orders against the oracle; pipeline: every call
     took the general path and cut exactly the rows above LONG_ROW into
-    pieces; else: no call did (the wave path)."""
+    pieces; else: no call did (the wave path). Returns the four calls'
+    piece counts and what the library wrote to stderr."""
     dims, sa, sb = case
     a, b = Csr.from_csr_arrays(dims, *sa), Csr.from_csr_arrays(dims, *sb)
-    monkeypatch.setenv("BSM_SS_DEBUG", "1")
+    monkeypatch.setenv("BSM_SS_DEBUG", debug)
     capfd.readouterr()
     for op, ref in [(Csr.add_sparse, orc.add_sparse), (Csr.sub_sparse, orc.sub_sparse)]:
         cmp(op(a, b), *ref(arrays(a), arrays(b)))
         cmp(op(b, a), *ref(arrays(b), arrays(a)))
-    lines = DEBUG_LINE.findall(capfd.readouterr().err)
+    err = capfd.readouterr().err
+    lines = DEBUG_LINE.findall(err)
     if pipeline:
         assert len(lines) == 4, lines
         for n_long, n_chunks, n_pieces in lines:
             assert int(n_long) == n_long_rows(sa, sb) and int(n_pieces) >= int(n_long) > 0, lines
     else:
         assert lines == []
+    return [int(n_pieces) for _, _, n_pieces in lines], err
 
 
 # ---- 1. dispatch boundaries -------------------------------------------------
@@ -363,17 +368,20 @@ _records = {}   # setting -> {case: record} of the child that ran it
 _dead = []      # why no further child may start (a child ended by a signal or timed out)
 
 
-def _child(env_name, tmp_path_factory):
+def _child(env_name, tmp_path_factory, settings=None, cases=W.CHILD_CASES):
+    """The records of the one child of setting env_name (started at its first
+    use): `cases` under the switches `settings` (ENVS[env_name] and
+    BSM_SS_DEBUG=1 when not given)."""
     if env_name in _records:
         return _records[env_name]
     if _dead:
         pytest.fail("not started: " + _dead[0])
     out = tmp_path_factory.mktemp("addsub_" + env_name) / "records.json"
     env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    env.update(ENVS[env_name], BSM_SS_DEBUG="1")
+    env.update(dict(ENVS[env_name], BSM_SS_DEBUG="1") if settings is None else settings)
     log = ""
     try:
-        r = subprocess.run([sys.executable, "-u", WORKER, str(out)] + W.CHILD_CASES, env=env,
+        r = subprocess.run([sys.executable, "-u", WORKER, str(out)] + cases, env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
         log = r.stdout.decode(errors="replace")
         if r.returncode < 0 or r.returncode in (134, 139):
@@ -465,3 +473,69 @@ def test_special_float_values(orc, capfd, monkeypatch, dtype, path):
     case = special_case(dtype)
     assert n_long_rows(case[1], case[2]) == 2 and longest(case[1]) + longest(case[2]) <= W.WROW_CAP
     check(orc, capfd, monkeypatch, case, pipeline=path == "general", cmp=assert_csr_bits_or_nan)
+
+
+# ---- 8. the diagnostic levels of BSM_SS_DEBUG ---------------------------------
+# Levels 2 and 4 hand piece_merge / piece_split a stamp buffer, level 3 ends
+# every phase with a synchronise: each on the smallest long-row operands, on
+# the general path (BSM_SS_WAVE=0: the row of 65 entries alone would take the
+# wave path), with the result still the oracle's and as many pieces as under
+# level 1.
+DIAG_CASES = [f"diag:{kind}:{dt}" for kind in ("row65", "cap1") for dt in ("f64", "u32")]
+DIAG_ENVS = {"level2": {"BSM_SS_WAVE": "0", "BSM_SS_SPLIT": "0", "BSM_SS_DEBUG": "2"},
+             "level3": {"BSM_SS_WAVE": "0", "BSM_SS_DEBUG": "3"}}
+MERGE_LINE = re.compile(r"\[bsm ss debug\] piece_merge over (\d+) pieces: per piece staging ")
+SPLIT_LINE = re.compile(r"\[bsm ss split\] (\d+) pieces, mean ")
+TIME_LINE = re.compile(r"^\[bsm ss time\] (.+?) +\d+\.\d{3} ms$", re.M)
+TIME_LABELS = ["count + long-row scan", "long rows + extents", "row maxima + counts", "pieces", "piece_split + scan",
+               "row scan + nnz", "output alloc", "fill + copy", "scope exit (frees)"]
+
+
+def default_pieces(orc, capfd, monkeypatch, case):
+    """The four calls' piece counts under level 1 (and the results against the oracle)."""
+    monkeypatch.setenv("BSM_SS_WAVE", "0")
+    return check(orc, capfd, monkeypatch, W.build(case))[0]
+
+
+def diag_child(level, case, tmp_path_factory):
+    """What the child of that level wrote while it ran `case`, its result checked."""
+    recs = _child(level, tmp_path_factory, DIAG_ENVS[level], DIAG_CASES)
+    rec, log = recs.get(case), recs["__log__"]
+    if rec is None:
+        pytest.fail(f"no record of {case} under {level}; " + (_dead[0] if _dead else log[-3000:]))
+    for k in SWITCHES:  # the child really ran under the setting
+        assert rec["env"].get(k) == DIAG_ENVS[level].get(k), rec["env"]
+    assert rec["ok"], f"{rec['call']}: {rec['what']} differs first at {rec['first_mismatch']}"
+    return log[log.index(f"BEGIN {case}\n"):log.index(f"END {case} ")]
+
+
+@gpu
+@pytest.mark.parametrize("case", DIAG_CASES)
+def test_debug_level_2_piece_merge_stamps(orc, capfd, monkeypatch, tmp_path_factory, case):
+    """BSM_SS_DEBUG=2 under BSM_SS_SPLIT=0 (a child): piece_merge writes its
+    six stamps per piece and the host reports them, once per call."""
+    pieces = default_pieces(orc, capfd, monkeypatch, case)
+    part = diag_child("level2", case, tmp_path_factory)
+    assert [int(p) for _, _, p in DEBUG_LINE.findall(part)] == pieces, part[-2000:]
+    assert [int(p) for p in MERGE_LINE.findall(part)] == pieces, part[-2000:]
+
+
+@gpu
+@pytest.mark.parametrize("case", DIAG_CASES)
+def test_debug_level_3_phase_times(orc, capfd, monkeypatch, tmp_path_factory, case):
+    """BSM_SS_DEBUG=3 (read once per process: a child): every phase of every
+    call ends with a synchronise and a line, the labels in their order."""
+    pieces = default_pieces(orc, capfd, monkeypatch, case)
+    part = diag_child("level3", case, tmp_path_factory)
+    assert [int(p) for _, _, p in DEBUG_LINE.findall(part)] == pieces, part[-2000:]
+    assert TIME_LINE.findall(part) == TIME_LABELS * 4, part[-3000:]
+
+
+@gpu
+@pytest.mark.parametrize("case", DIAG_CASES)
+def test_debug_level_4_piece_split_stamps(orc, capfd, monkeypatch, case):
+    """BSM_SS_DEBUG=4 (read per call: in this process): piece_split writes
+    its nine stamps per piece and the host reports them, once per call."""
+    pieces = default_pieces(orc, capfd, monkeypatch, case)
+    got, err = check(orc, capfd, monkeypatch, W.build(case), debug="4")
+    assert got == pieces and [int(p) for p in SPLIT_LINE.findall(err)] == pieces, err[-2000:]
