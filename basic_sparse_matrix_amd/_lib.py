@@ -134,6 +134,14 @@ SIGNATURES = [
     ("bsm_nd_factor_updown", _int, [_vp, _int, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_solve_sparse", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _pp, _vp]),
     ("bsm_dev_nd_factor_solve_sparse", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("bsm_nd_factor_create_schur", _int, [_vp, _int, _vp, _u64, ctypes.POINTER(_vp)]),
+    ("bsm_nd_factor_schur_info", _int, [_vp, _u64p, _vp]),
+    ("bsm_nd_factor_schur", _int, [_vp, _vp, _vp, _u64]),
+    ("bsm_dev_nd_factor_schur", _int, [_vp, _vp, _vp, _u64, _vp]),
+    ("bsm_nd_factor_schur_condense", _int, [_vp, _pp, _u64, _pp]),
+    ("bsm_nd_factor_schur_expand", _int, [_vp, _pp, _u64, _pp, _pp]),
+    ("bsm_dev_nd_factor_schur_condense", _int, [_vp, _vp, _u64, _vp, _vp]),
+    ("bsm_dev_nd_factor_schur_expand", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_refactor_partial", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     ("bsm_nd_factor_refactor_since", _int, [_vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_pattern_info", _int, [_vp, _u64p, ctypes.POINTER(_int)]),
@@ -142,6 +150,7 @@ SIGNATURES = [
     ("bsm_dev_nd_factor_sddmm", _int, [_vp, _int, _u64, _u64, _vp, _vp, _vp, _vp]),
     ("bsm_nd_factor_free", None, [_vp]),
     ("bsm_nd_analyse", _int, [_u64, _vp, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
+    ("bsm_nd_analyse_last", _int, [_u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u64p, _vp, _u64, _u64p]),
     ("bsm_nd_cache_clear", _int, []),
     ("bsm_nd_cache_info", _int, [_u64p, _u64p, _u64p, _u64p]),
     ("bsm_dev_gen_row_ptr", _int, [_u64, _u64, _u64, _u32, _int, _u32, _u32, _vp, _vp, _u64, _vp]),

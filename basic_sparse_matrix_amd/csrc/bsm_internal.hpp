@@ -10,6 +10,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/bsm.h"
 
@@ -286,6 +287,11 @@ struct bsm_nd_factor {
     // an update / downdate has rewritten pivot panels since the last numeric factorisation: the children's update
     // blocks left in the trailing tiles no longer belong to them, so a partial refactor must not pull them (under mu)
     bool stale_blocks = false;
+    // The Schur set (bsm_nd_factor_create_schur): the vertices the plan's root owns, in the
+    // caller's order (empty: none; fixed for the handle's life), and on the device, as int32, each one's place among
+    // the root's columns followed by the inverse map (the caller's index of each root column)
+    std::vector<uint64_t> schur_idx;
+    bsm::DBuf schur_map;
 };
 
 namespace bsm {
@@ -403,7 +409,16 @@ int solve_dispatch_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* b_de
 // the kept nd factor (kernels_nd.hip and kernels_nd_*.hip); all synchronous on s. b_dev / x_dev:
 // ROW-major n x k, as solve_dispatch_nd's
 // factor_dtype: BSM_F64 or BSM_F32; where it is not a's, a's values are converted first
-int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s);
+// idx (m distinct vertices < n, checked by the caller; m == 0: none): the Schur set, the root front's own columns
+int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s,
+                     const uint64_t* idx = nullptr, uint64_t m = 0);
+// The Schur complement of a kept factor made with a set (kernels_nd_schur.hip); all synchronous
+// on s. out_dev: m x m of f's dtype, column-major with leading dimension ld >= m, in the caller's order of the
+// set. b_dev / x_dev: ROW-major n x k, g_dev / xg_dev: ROW-major m x k, all of f's dtype.
+int nd_factor_schur(const bsm_nd_factor* f, const bsm_csr* a, void* out_dev, uint64_t ld, hipStream_t s);
+int nd_factor_schur_condense(const bsm_nd_factor* f, uint64_t k, const void* b_dev, void* g_dev, hipStream_t s);
+int nd_factor_schur_expand(const bsm_nd_factor* f, uint64_t k, const void* b_dev, const void* xg_dev, void* x_dev,
+                           hipStream_t s);
 // system: BSM_ND_SYS_A / _L / _LT (bsm.h)
 int nd_factor_solve(const bsm_nd_factor* f, int system, uint64_t k, uint64_t n, const void* b_dev, void* x_dev,
                     hipStream_t s);

@@ -13,6 +13,7 @@
 
 #include "bsm_internal.hpp"
 #include "eig_rule.hpp"
+#include "nd.hpp"
 
 namespace bsm {
 
@@ -1089,6 +1090,129 @@ int bsm_nd_factor_create_as(const bsm_csr* a, int factor_dtype, bsm_nd_factor** 
                 "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
     BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
     return nd_factor_create(a, factor_dtype, out, s);
+}
+
+// ---- the Schur complement on a chosen set (kernels_nd_schur.hip) ----
+int bsm_nd_factor_create_schur(const bsm_csr* a, int factor_dtype, const uint64_t* idx, uint64_t m,
+                               bsm_nd_factor** out) {
+    BSM_REQUIRE(a && out && (m == 0 || idx), BSM_ERR_INVALID, "null argument");
+    BSM_REQUIRE(factor_dtype == BSM_F64 || factor_dtype == BSM_F32, BSM_ERR_INVALID,
+                "nd factor: factor_dtype must be BSM_F64 or BSM_F32, got %d", factor_dtype);
+    // the set, before any device is asked for and before anything is allocated for the factor
+    uint64_t bad = 0;
+    const int lc = nd_last_check((int64_t)a->rows, idx, m, &bad);
+    BSM_REQUIRE(lc != 1, BSM_ERR_INVALID, "nd factor schur: idx[%llu] = %llu, the matrix is %llu x %llu",
+                (unsigned long long)bad, (unsigned long long)idx[bad], (unsigned long long)a->rows,
+                (unsigned long long)a->cols);
+    BSM_REQUIRE(lc != 2, BSM_ERR_INVALID, "nd factor schur: idx[%llu] = %llu repeats an earlier entry",
+                (unsigned long long)bad, (unsigned long long)idx[bad]);
+    BSM_REQUIRE(m <= (uint64_t)ND_LAST_MAX, BSM_ERR_UNSUPPORTED,
+                "nd factor schur: a set of %llu vertices; at most %lld (its front is dense)", (unsigned long long)m,
+                (long long)ND_LAST_MAX);
+    hipStream_t s;
+    BSM_TRY(ctx_stream(&s));
+    BSM_REQUIRE(a->rows == a->cols, BSM_ERR_PANIC,
+                "solve: cholesky_decomp().unwrap() on a non-square matrix panics (lib.rs:20)");
+    BSM_REQUIRE(a->dtype == BSM_F32 || a->dtype == BSM_F64, BSM_ERR_INVALID, "f32/f64 only");
+    return nd_factor_create(a, factor_dtype, out, s, idx, m);
+}
+
+int bsm_nd_factor_schur_info(const bsm_nd_factor* f, uint64_t* m, uint64_t* idx_out) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    if (m) *m = f->schur_idx.size();  // fixed for the handle's life: no lock
+    if (idx_out) std::copy(f->schur_idx.begin(), f->schur_idx.end(), idx_out);
+    return BSM_OK;
+}
+
+// the checks of the three calls that need no device: the handles, the set, the buffers
+static int schur_check(const bsm_nd_factor* f, const char* what) {
+    BSM_REQUIRE(f, BSM_ERR_INVALID, "null handle");
+    BSM_REQUIRE(!f->schur_idx.empty(), BSM_ERR_INVALID,
+                "nd factor %s: the factor was made without a Schur set (bsm_nd_factor_create_schur)", what);
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_schur(const bsm_nd_factor* f, const bsm_csr* a, void* out, uint64_t ld, void* stream) {
+    BSM_REQUIRE(f && a, BSM_ERR_INVALID, "null handle");
+    BSM_TRY(schur_check(f, "schur"));
+    BSM_REQUIRE(out, BSM_ERR_INVALID, "null argument (out)");
+    BSM_REQUIRE(ld >= f->schur_idx.size(), BSM_ERR_INVALID,
+                "nd factor schur: ld = %llu is less than the set's %llu vertices", (unsigned long long)ld,
+                (unsigned long long)f->schur_idx.size());
+    BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_schur(f, a, out, ld, static_cast<hipStream_t>(stream));
+}
+
+int bsm_nd_factor_schur(const bsm_nd_factor* f, const bsm_csr* a, void* out, uint64_t ld) {
+    BSM_REQUIRE(f && a, BSM_ERR_INVALID, "null handle");
+    BSM_TRY(schur_check(f, "schur"));
+    BSM_REQUIRE(out, BSM_ERR_INVALID, "null argument (out)");
+    const uint64_t m = f->schur_idx.size();
+    BSM_REQUIRE(ld >= m, BSM_ERR_INVALID, "nd factor schur: ld = %llu is less than the set's %llu vertices",
+                (unsigned long long)ld, (unsigned long long)m);
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    const size_t es = dtype_size(f->dtype);
+    DBuf d;
+    BSM_TRY(d.alloc((size_t)m * m * es));
+    BSM_TRY(nd_factor_schur(f, a, d.p, m, s));
+    BSM_HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * es, d.p, (size_t)m * es, (size_t)m * es, (size_t)m,
+                                 hipMemcpyDeviceToHost, s));
+    BSM_HIP_TRY(hipStreamSynchronize(s));
+    return BSM_OK;
+}
+
+int bsm_dev_nd_factor_schur_condense(const bsm_nd_factor* f, const void* b, uint64_t k, void* g, void* stream) {
+    BSM_TRY(schur_check(f, "schur_condense"));
+    BSM_REQUIRE(k == 0 || (b && g), BSM_ERR_INVALID, "null argument");
+    BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_schur_condense(f, k, b, g, static_cast<hipStream_t>(stream));
+}
+
+int bsm_dev_nd_factor_schur_expand(const bsm_nd_factor* f, const void* b, uint64_t k, const void* x_gamma, void* x,
+                                   void* stream) {
+    BSM_TRY(schur_check(f, "schur_expand"));
+    BSM_REQUIRE(k == 0 || (b && x_gamma && x), BSM_ERR_INVALID, "null argument");
+    BSM_TRY(nd_factor_on_device(f));
+    return nd_factor_schur_expand(f, k, b, x_gamma, x, static_cast<hipStream_t>(stream));
+}
+
+static int schur_cols_check(uint64_t k, const void* const* cols, const char* name) {
+    BSM_REQUIRE(k == 0 || cols, BSM_ERR_INVALID, "null argument (%s)", name);
+    for (uint64_t j = 0; j < k; ++j)
+        BSM_REQUIRE(cols[j], BSM_ERR_INVALID, "null column pointer %llu (%s)", (unsigned long long)j, name);
+    return BSM_OK;
+}
+
+int bsm_nd_factor_schur_condense(const bsm_nd_factor* f, const void* const* b_cols, uint64_t k, void* const* g_cols) {
+    BSM_TRY(schur_check(f, "schur_condense"));
+    BSM_TRY(schur_cols_check(k, b_cols, "b_cols"));
+    BSM_TRY(schur_cols_check(k, g_cols, "g_cols"));
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    const uint64_t m = f->schur_idx.size();
+    DBuf b, g;
+    BSM_TRY(upload_columns(f->dtype, f->n, k, b_cols, b, s));
+    BSM_TRY(g.alloc(m * k * dtype_size(f->dtype)));
+    BSM_TRY(nd_factor_schur_condense(f, k, b.p, g.p, s));
+    return download_columns(f->dtype, m, k, g.p, g_cols, s);
+}
+
+int bsm_nd_factor_schur_expand(const bsm_nd_factor* f, const void* const* b_cols, uint64_t k,
+                               const void* const* xg_cols, void* const* x_cols) {
+    BSM_TRY(schur_check(f, "schur_expand"));
+    BSM_TRY(schur_cols_check(k, b_cols, "b_cols"));
+    BSM_TRY(schur_cols_check(k, xg_cols, "x_gamma_cols"));
+    BSM_TRY(schur_cols_check(k, x_cols, "x_cols"));
+    hipStream_t s;
+    BSM_TRY(nd_factor_stream(f, &s));
+    const uint64_t m = f->schur_idx.size();
+    DBuf b, xg, x;
+    BSM_TRY(upload_columns(f->dtype, f->n, k, b_cols, b, s));
+    BSM_TRY(upload_columns(f->dtype, m, k, xg_cols, xg, s));
+    BSM_TRY(x.alloc(f->n * k * dtype_size(f->dtype)));
+    BSM_TRY(nd_factor_schur_expand(f, k, b.p, xg.p, x.p, s));
+    return download_columns(f->dtype, f->n, k, x.p, x_cols, s);
 }
 
 // the refined solve's checks, all before any device is asked for

@@ -1077,7 +1077,6 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
                     const T* Dinv, const void* b_dev, void* x_dev, NdSolveTmp& t, bool folded, int* d_status,
                     hipStream_t s, int system = BSM_ND_SYS_A) {
     const NdPtrs p = nd_ptrs(C);
-    const int cus = g.cus;
     T* const bp = t.bpb.as<T>();
     T* const V = t.vb.as<T>();
     const bool fwd = !folded && system != BSM_ND_SYS_LT, bwd = system != BSM_ND_SYS_L;
@@ -1086,33 +1085,13 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
         nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, perm, static_cast<const T*>(b_dev), bp);
         BSM_HIP_TRY(hipGetLastError());
     }
-    // Levels with fewer (node, column) pairs than CUs run their solves by
-    // tiles (nd_forward_tiles / nd_backward_tiles: a front's chain of pivot
-    // tiles on many waves), the others one workgroup per pair (nd_forward /
-    // nd_backward: less bookkeeping per front). Same bits either way.
-    // BSM_ND_FWD_TILES / BSM_ND_BWD_TILES = 0: never, 1: every level.
-    auto by_tiles = [&](int mode, int64_t pairs) { return mode == 1 || (mode == 2 && pairs < cus); };
     BSM_HIP_TRY(hipMemsetAsync(t.tfl.p, 0, (t.n_tf + 1) * sizeof(int), s));
     int* const d_yf = t.tfl.as<int>();
     int* const d_xf = d_yf + t.n_pf;
     int* const d_ftk = d_xf + t.n_pf;
     int* const d_btk = d_ftk + C.n_levels;
-    const int64_t fwd_grid = (int64_t)cus * g.fper;
-    for (int32_t lv = 0; lv < C.n_levels && fwd; ++lv) {
-        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
-        if (c <= 0) continue;
-        if (by_tiles(opt.fwd_tiles, c * (int64_t)k)) {
-            const int64_t f0 = C.ftask_off[(size_t)lv], nf = C.ftask_off[(size_t)lv + 1] - f0;
-            const int64_t grid = std::min<int64_t>(nf * (int64_t)k, fwd_grid);
-            if (grid <= 0) continue;  // fronts without rows (no pivots, no front rows)
-            nd_forward_tiles<T><<<(unsigned)grid, 64, 0, s>>>(p.nodes, p.ftask + f0, nf, (int)k, N, bp, V, C.vtot, F,
-                                                              Dinv, p.ri, d_yf, d_ftk + lv, d_status);
-        } else {
-            nd_forward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
-                                                                        p.ri);
-        }
-        BSM_HIP_TRY(hipGetLastError());
-    }
+    if (fwd)
+        BSM_TRY(NdHost<T>::forward_levels(C, opt, g, N, k, F, Dinv, bp, V, d_yf, d_ftk, d_status, s, C.n_levels));
     if (system == BSM_ND_SYS_L && C.nn > 0) {
         nd_y_out<T><<<dim3((unsigned)C.nn, (unsigned)k), 256, 0, s>>>(p.nodes, N, V, C.vtot, bp);
         BSM_HIP_TRY(hipGetLastError());
@@ -1122,7 +1101,8 @@ int nd_solve_passes(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64
         nd_y_in<T><<<dim3((unsigned)C.nn, (unsigned)k), 256, 0, s>>>(p.nodes, N, bp, V, C.vtot);
         BSM_HIP_TRY(hipGetLastError());
     }
-    if (bwd) BSM_TRY(NdHost<T>::backward_levels(C, opt, g, N, k, F, Dinv, bp, V, d_xf, d_btk, d_status, s));
+    if (bwd)
+        BSM_TRY(NdHost<T>::backward_levels(C, opt, g, N, k, F, Dinv, bp, V, d_xf, d_btk, d_status, s, C.n_levels));
     stage_mark("nd_backward", s);
     nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, perm, bp, static_cast<T*>(x_dev));
     BSM_HIP_TRY(hipGetLastError());
@@ -1391,6 +1371,7 @@ int nd_factor_numeric_t(const bsm_csr* a, bsm_nd_factor& f, const NdCached& C, c
     return BSM_OK;
 }
 
+// f.schur_idx (non-empty): the plan whose root owns those vertices, the factor's alone (§4.9o)
 template <typename T>
 int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
     stage_reset(s);
@@ -1399,9 +1380,24 @@ int nd_factor_create_t(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
     NdLay lay = opt.lay;
     lay.plain = lay.plain || a->nnz >= ((uint64_t)1 << 31);  // as nd_solve
     std::shared_ptr<NdCached> pc;
+    const std::vector<int64_t> last(f.schur_idx.begin(), f.schur_idx.end());
     // no kept storage asked for on a new plan: the factor's fronts are its own
-    BSM_TRY(nd_obtain_plan(a, opt, lay, 0, s, pc));
+    BSM_TRY(nd_obtain_plan(a, opt, lay, 0, s, pc, &last));
     NdCached& C = *pc;
+    if (!last.empty()) {
+        // each vertex's place among the root's columns (its rank in the sorted set), then the inverse map
+        const size_t m = last.size();
+        std::vector<int32_t> ord(m), map(2 * m);
+        for (size_t i = 0; i < m; ++i) ord[i] = (int32_t)i;
+        std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return last[(size_t)x] < last[(size_t)y]; });
+        for (size_t r = 0; r < m; ++r) {
+            map[(size_t)ord[r]] = (int32_t)r;
+            map[m + r] = ord[r];
+        }
+        BSM_TRY(f.schur_map.alloc(2 * m * sizeof(int32_t)));
+        BSM_HIP_TRY(hipMemcpyAsync(f.schur_map.p, map.data(), 2 * m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        BSM_HIP_TRY(hipStreamSynchronize(s));  // `map` goes away
+    }
     nd_trace(opt, C, N, sizeof(T));
     const size_t fr_b = (size_t)C.f_elems * sizeof(T), dv_b = (size_t)std::max<int64_t>(C.dinv_elems, 1) * sizeof(T);
     BSM_TRY(nd_alloc_numeric(f.fr, fr_b, nullptr));
@@ -1554,17 +1550,62 @@ int nd_factor_numeric(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s) {
                               : nd_factor_numeric_t<float>(a, f, *pc, nd_options(), s);
 }
 
+// The forward levels of a solve, bottom-up over the fronts of levels [0,
+// lv_end): b in the new order in bp, y and the update vectors into V. d_yf /
+// d_ftk: the pass's cleared flags and tickets, as backward_levels'.
+// Levels with fewer (node, column) pairs than CUs run their solves by
+// tiles (nd_forward_tiles / nd_backward_tiles: a front's chain of pivot
+// tiles on many waves), the others one workgroup per pair (nd_forward /
+// nd_backward: less bookkeeping per front). Same bits either way.
+// BSM_ND_FWD_TILES / BSM_ND_BWD_TILES = 0: never, 1: every level.
+template <typename T>
+int NdHost<T>::forward_levels(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
+                              const T* Dinv, const T* bp, T* V, int* d_yf, int* d_ftk, int* d_status, hipStream_t s,
+                              int32_t lv_end) {
+    const NdPtrs p = nd_ptrs(C);
+    const int64_t fwd_grid = (int64_t)g.cus * g.fper;
+    for (int32_t lv = 0; lv < lv_end; ++lv) {
+        const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
+        if (c <= 0) continue;
+        if (opt.fwd_tiles == 1 || (opt.fwd_tiles == 2 && c * (int64_t)k < g.cus)) {
+            const int64_t f0 = C.ftask_off[(size_t)lv], nf = C.ftask_off[(size_t)lv + 1] - f0;
+            const int64_t grid = std::min<int64_t>(nf * (int64_t)k, fwd_grid);
+            if (grid <= 0) continue;  // fronts without rows (no pivots, no front rows)
+            nd_forward_tiles<T><<<(unsigned)grid, 64, 0, s>>>(p.nodes, p.ftask + f0, nf, (int)k, N, bp, V, C.vtot, F,
+                                                              Dinv, p.ri, d_yf, d_ftk + lv, d_status);
+        } else {
+            nd_forward<T><<<dim3((unsigned)c, (unsigned)k), 256, 0, s>>>(p.nodes, p.lvl + o, N, bp, V, C.vtot, F, Dinv,
+                                                                        p.ri);
+        }
+        BSM_HIP_TRY(hipGetLastError());
+    }
+    return BSM_OK;
+}
+
+// b (row-major n x k, A's order) into bp (new order, a column after the other), or xp back into x
+template <typename T>
+int NdHost<T>::permute_launch(bool gather, const NdCached& C, int64_t N, uint64_t k, const T* src, T* dst,
+                              hipStream_t s) {
+    const NdPtrs p = nd_ptrs(C);
+    if (gather) nd_gather<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, src, dst);
+    else nd_scatter<T><<<nd_blocks(N, 256), 256, 0, s>>>(N, (int64_t)k, p.perm, src, dst);
+    BSM_HIP_TRY(hipGetLastError());
+    return BSM_OK;
+}
+
 // The backward levels of a solve, top-down over every front: y over each
 // front's pivots in V, x into bp. d_xf / d_btk: the pass's cleared flags (one
 // per node, column and pivot tile) and tickets (one per level). Levels with
-// fewer (node, column) pairs than CUs run by tiles (nd_solve_passes).
+// fewer (node, column) pairs than CUs run by tiles (forward_levels). Levels
+// [0, lv_end): all of them for a solve; without the root's for the Schur
+// complement's expansion (§4.9o), which has put x over the root's columns itself.
 template <typename T>
 int NdHost<T>::backward_levels(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k,
                                const T* F, const T* Dinv, T* bp, T* V, int* d_xf, int* d_btk, int* d_status,
-                               hipStream_t s) {
+                               hipStream_t s, int32_t lv_end) {
     const NdPtrs p = nd_ptrs(C);
     const int64_t bwd_grid = (int64_t)g.cus * g.bper;
-    for (int32_t lv = C.n_levels - 1; lv >= 0; --lv) {
+    for (int32_t lv = lv_end - 1; lv >= 0; --lv) {
         const int64_t o = C.lvl_off[(size_t)lv], c = C.lvl_off[(size_t)lv + 1] - o;
         if (c <= 0) continue;
         if (opt.bwd_tiles == 1 || (opt.bwd_tiles == 2 && c * (int64_t)k < g.cus)) {
@@ -1605,10 +1646,12 @@ int nd_factor_sddmm(const bsm_nd_factor* f, int dtype, uint64_t k, const void* u
                           (const int32_t*)(pb + nd_pattern_rp_bytes((int64_t)f->n)), k, u, v, out, s);
 }
 
-int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s) {
+int nd_factor_create(const bsm_csr* a, int factor_dtype, bsm_nd_factor** out, hipStream_t s, const uint64_t* idx,
+                     uint64_t m) {
     BSM_REQUIRE(a->rows < ((uint64_t)1 << 31), BSM_ERR_UNSUPPORTED, "solve nd: n >= 2^31");
     BSM_REQUIRE(a->dtype == BSM_F64 || a->dtype == BSM_F32, BSM_ERR_INVALID, "solve: f32/f64 only");
     auto f = std::make_unique<bsm_nd_factor>();
+    f->schur_idx.assign(idx, idx + m);
     f->dtype = factor_dtype;
     f->src_dtype = a->dtype;
     f->device = a->device;

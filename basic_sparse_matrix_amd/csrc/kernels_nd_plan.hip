@@ -498,7 +498,9 @@ size_t nd_plan_bytes_bound(const NdPlan& P, NdLay lay) {
 // es > 0: the fronts (es-byte values) are allocated into C.fr on a helper
 // thread while the layout, the packing and the plan's upload run: a first
 // solve's 5 GB hipMalloc (C5) then costs no time of its own
-int nd_build_plan(const bsm_csr* a, int64_t leaf, NdLay lay, int threads, size_t es, hipStream_t s, NdCached& C) {
+// last: the vertices the root owns (nd_analyse), or null
+int nd_build_plan(const bsm_csr* a, int64_t leaf, NdLay lay, int threads, size_t es, hipStream_t s, NdCached& C,
+                  const std::vector<int64_t>* last = nullptr) {
     const int64_t N = (int64_t)a->rows;
     // A's pattern to the host for the analysis
     char* stg = nullptr;
@@ -512,7 +514,8 @@ int nd_build_plan(const bsm_csr* a, int64_t leaf, NdLay lay, int threads, size_t
     BSM_HIP_TRY(hipStreamSynchronize(s));
     stage_mark("nd_pattern_d2h", s);
     NdPlan P;
-    const int arc = nd_analyse(N, rp, cl, leaf, threads, P);
+    const int arc = nd_analyse(N, rp, cl, leaf, threads, P, last ? last->data() : nullptr,
+                               last ? (int64_t)last->size() : 0);
     BSM_REQUIRE(arc == 0, BSM_ERR_UNSUPPORTED,
                 "cholesky: rows must have strictly increasing columns (get_row_complete semantics)");
     std::thread pre;
@@ -902,10 +905,17 @@ int nd_pattern_same(const bsm_csr* a, const bsm_nd_factor& f, hipStream_t s) {
 // The plan of a's pattern: the one on the handle, else the cross-handle
 // cache's, else a new one (then kept in both, as the switches allow). es > 0:
 // a new plan allocates its kept numeric storage while it is built.
+// last (non-empty): the plan whose root owns these vertices (§4.9o), always a
+// new one and kept nowhere but with the caller: neither cache's key knows the
+// set, so neither ever holds, or hands out, such a plan.
 int nd_obtain_plan(const bsm_csr* a, const NdOpts& opt, NdLay lay, size_t es, hipStream_t s,
-                   std::shared_ptr<NdCached>& pc) {
+                   std::shared_ptr<NdCached>& pc, const std::vector<int64_t>* last) {
     const bool cache = opt.cache, shared = opt.shared;
     const int64_t leaf = opt.leaf;
+    if (last && !last->empty()) {
+        pc = std::make_shared<NdCached>();
+        return nd_build_plan(a, leaf, lay, opt.threads, es, s, *pc, last);
+    }
     if (cache) {
         std::lock_guard<std::mutex> lk(a->plan_mu);
         auto c = std::static_pointer_cast<NdCached>(a->nd_plan);

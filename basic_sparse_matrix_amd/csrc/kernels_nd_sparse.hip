@@ -159,7 +159,7 @@ int nd_factor_solve_sparse_t(const bsm_nd_factor& f, uint64_t k, const uint64_t*
         stage_mark("nd_sparse_forward", s);
         if (all) {
             BSM_TRY(NdHost<T>::backward_levels(C, opt, g, N, kc, F, Dinv, bp, V, tfl.as<int>(), tfl.as<int>() + n_pf,
-                                          d_status, s));
+                                               d_status, s, C.n_levels));
         } else {
             for (size_t li = bw.levels.size(); li-- > 0;) {
                 const int32_t a0 = bw.first(li), cnt = bw.last(li) - a0;

@@ -33,6 +33,17 @@ struct NdPlan {
 // lower triangle (j <= i, as the band path reads it) mirrored, so the graph
 // has an edge {i, j} for every stored j < i. leaf: largest part not split
 // further; threads: worker threads for the bisection and the symbolic pass.
-int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t leaf, int threads, NdPlan& plan);
+// last (m distinct vertices < n, any order; nd_last_check's rule; m == 0: none):
+// the root node owns exactly these vertices (perm[n - m .. n) = sorted(last))
+// and its only child (kids[0]; kids[1] = -1) is the bisection tree of the
+// graph induced on the others.
+int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t leaf, int threads, NdPlan& plan,
+               const int64_t* last = nullptr, int64_t m = 0);
+
+// The largest set nd_analyse's `last` may name: its front is dense, (64 ceil(m / 64))^2 values (2 GiB of f64 here)
+constexpr int64_t ND_LAST_MAX = 16384;
+// 0: `last` holds m distinct vertices < n; 1: entry *bad is >= n; 2: entry *bad repeats an earlier one.
+// Allocates m indices, nothing else.
+int nd_last_check(int64_t n, const uint64_t* last, uint64_t m, uint64_t* bad);
 
 }  // namespace bsm

@@ -1,8 +1,8 @@
 // nd_internal.hpp -- what the nested-dissection solver's files share: the plan's types and small
 // helpers, and the host functions that cross a file boundary. kernels_nd_plan.hip builds and caches plans;
 // kernels_nd.hip factors and solves on one; the kept factor's other answers each have a file (kernels_nd_selinv /
-// _updown / _sparse / _partial.hip). Every kernel is defined in one file: another file reaches it through a host
-// function declared here (NdHost: instantiated for float and double by kernels_nd.hip).
+// _updown / _sparse / _partial / _schur.hip). Every kernel is defined in one file: another file reaches it through a
+// host function declared here (NdHost: instantiated for float and double by kernels_nd.hip).
 #pragma once
 
 #include <atomic>
@@ -179,7 +179,7 @@ struct NdGrid {
 // ---- kernels_nd_plan.hip ----
 NdOpts nd_options();
 int nd_obtain_plan(const bsm_csr* a, const NdOpts& opt, NdLay lay, size_t es, hipStream_t s,
-                   std::shared_ptr<NdCached>& pc);
+                   std::shared_ptr<NdCached>& pc, const std::vector<int64_t>* last = nullptr);
 void nd_trace(const NdOpts& opt, const NdCached& C, int64_t N, size_t es);
 void nd_cache_trim(size_t budget, const NdCached* keep);
 int nd_alloc_numeric(DBuf& b, size_t bytes, const NdCached* keep);
@@ -188,7 +188,8 @@ int nd_pattern_same(const bsm_csr* a, const bsm_nd_factor& f, hipStream_t s);
 
 // ---- kernels_nd.hip ----
 // Its kernels for the other files, per dtype: the persistent kernels' occupancy, nd_factor on a list of tasks, one
-// level of nd_forward_path / nd_backward_path, and the dense backward levels
+// level of nd_forward_path / nd_backward_path, the dense forward and backward levels (up to a level), and the
+// right-hand sides' permutation
 template <typename T>
 struct NdHost {
     static int grid(bool factor, bool solves, NdGrid& g);
@@ -197,8 +198,14 @@ struct NdHost {
                              const int2* tq, const NdPull* pd, unsigned long long* stamps, hipStream_t s);
     static int path_launch(bool forward, const NdCached& C, const ReachFront* act, unsigned cnt, unsigned kc, int64_t N,
                            T* bp, T* V, const T* F, const T* Dinv, hipStream_t s);
+    static int forward_levels(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
+                              const T* Dinv, const T* bp, T* V, int* d_yf, int* d_ftk, int* d_status, hipStream_t s,
+                              int32_t lv_end);
     static int backward_levels(const NdCached& C, const NdOpts& opt, const NdGrid& g, int64_t N, uint64_t k, const T* F,
-                               const T* Dinv, T* bp, T* V, int* d_xf, int* d_btk, int* d_status, hipStream_t s);
+                               const T* Dinv, T* bp, T* V, int* d_xf, int* d_btk, int* d_status, hipStream_t s,
+                               int32_t lv_end);
+    static int permute_launch(bool gather, const NdCached& C, int64_t N, uint64_t k, const T* src, T* dst,
+                              hipStream_t s);
 };
 int nd_status_end(bool factor, const int* d_status, NdDrainOnError& drain, const char* stage, hipStream_t s);
 int nd_factor_numeric(const bsm_csr* a, bsm_nd_factor& f, hipStream_t s);

@@ -425,7 +425,27 @@ struct Bisect {
 
 }  // namespace
 
-int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t leaf, int threads, NdPlan& plan) {
+int nd_last_check(int64_t n, const uint64_t* last, uint64_t m, uint64_t* bad) {
+    for (uint64_t i = 0; i < m; ++i)
+        if (last[i] >= (uint64_t)n) {
+            *bad = i;
+            return 1;
+        }
+    std::vector<std::pair<uint64_t, uint64_t>> o((size_t)m);  // (vertex, place in last)
+    for (uint64_t i = 0; i < m; ++i) o[(size_t)i] = {last[i], i};
+    std::sort(o.begin(), o.end());
+    uint64_t first = m;  // the first place in `last` that repeats an earlier entry
+    for (uint64_t i = 1; i < m; ++i)
+        if (o[(size_t)i].first == o[(size_t)i - 1].first) first = std::min(first, o[(size_t)i].second);
+    if (first < m) {
+        *bad = first;
+        return 2;
+    }
+    return 0;
+}
+
+int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t leaf, int threads, NdPlan& plan,
+               const int64_t* last, int64_t m) {
     plan = NdPlan{};
     plan.n = n;
     if (n <= 0) return 0;
@@ -451,7 +471,32 @@ int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t le
         bs.band = g.band;
         const char* tt = getenv("BSM_ND_TRACE");
         bs.trace = tt && atoi(tt) == 2;
-        bs.run_pool({std::move(all), root, 0, -1}, threads);
+        if (m <= 0) {
+            bs.run_pool({std::move(all), root, 0, -1}, threads);
+        } else {
+            // `last` is the root's own, as a cut's separator would be; the
+            // others (ascending) are its one child part, extracted as a
+            // cut's side A is and split from depth 1: the band shortcut of
+            // depth 0 is for the whole graph in its natural numbering
+            std::vector<int32_t> to((size_t)n, 0), rest;
+            for (int64_t i = 0; i < m; ++i) to[(size_t)last[i]] = -1;
+            rest.reserve((size_t)(n - m));
+            for (int64_t v = 0; v < n; ++v)
+                if (to[(size_t)v] == 0) {
+                    to[(size_t)v] = (int32_t)rest.size();
+                    rest.push_back((int32_t)v);
+                }
+            TNode& me = bs.node(root);
+            me.own.resize((size_t)m);
+            for (int64_t i = 0; i < m; ++i) me.own[(size_t)i] = (int32_t)last[i];
+            if (!rest.empty()) {
+                const int32_t kid = bs.new_node();
+                me.kid[0] = kid;
+                Bisect::Task tk{Part{}, kid, 1, -1};
+                Bisect::extract(all, rest, to, false, tk.p);
+                bs.run_pool(std::move(tk), threads);
+            }
+        }
     }
     plan.ms_bisect = ms_since(t0);
 
@@ -612,11 +657,15 @@ int nd_analyse(int64_t n, const int64_t* row_ptr, const int32_t* col, int64_t le
 }  // namespace bsm
 
 // ---- C-ABI: the analysis alone, on a host pattern (tests and diagnostics) ----
-extern "C" int bsm_nd_analyse(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
-                              int64_t* perm, int64_t* nodes, uint64_t cap, uint64_t* n_nodes, int64_t* st,
-                              uint64_t st_cap, uint64_t* st_len) {
-    if ((n && (!row_ptr || !col_idx)) || !n_nodes || !st_len) return BSM_ERR_INVALID;
+static int analyse_host(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
+                        const uint64_t* last, uint64_t m, int64_t* perm, int64_t* nodes, uint64_t cap,
+                        uint64_t* n_nodes, int64_t* st, uint64_t st_cap, uint64_t* st_len) {
+    if ((n && (!row_ptr || !col_idx)) || !n_nodes || !st_len || (m && !last)) return BSM_ERR_INVALID;
     if (n >= ((uint64_t)1 << 31)) return BSM_ERR_UNSUPPORTED;
+    uint64_t bad = 0;
+    if (bsm::nd_last_check((int64_t)n, last, m, &bad) != 0) return BSM_ERR_INVALID;
+    if (m > (uint64_t)bsm::ND_LAST_MAX) return BSM_ERR_UNSUPPORTED;
+    const std::vector<int64_t> lastv(last, last + m);
     const uint64_t nnz = n ? row_ptr[n] : 0;
     std::vector<int64_t> rp((size_t)n + 1);
     std::vector<int32_t> cl((size_t)nnz);
@@ -630,7 +679,8 @@ extern "C" int bsm_nd_analyse(uint64_t n, const uint64_t* row_ptr, const uint64_
     }
     bsm::NdPlan P;
     const char* te = getenv("BSM_ND_THREADS");
-    if (bsm::nd_analyse((int64_t)n, rp.data(), cl.data(), (int64_t)leaf, te ? atoi(te) : 4, P) != 0)
+    if (bsm::nd_analyse((int64_t)n, rp.data(), cl.data(), (int64_t)leaf, te ? atoi(te) : 4, P, lastv.data(),
+                        (int64_t)m) != 0)
         return BSM_ERR_UNSUPPORTED;
     *n_nodes = P.nodes.size();
     uint64_t total = 0;
@@ -655,4 +705,17 @@ extern "C" int bsm_nd_analyse(uint64_t n, const uint64_t* row_ptr, const uint64_
         }
     }
     return BSM_OK;
+}
+
+extern "C" int bsm_nd_analyse(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
+                              int64_t* perm, int64_t* nodes, uint64_t cap, uint64_t* n_nodes, int64_t* st,
+                              uint64_t st_cap, uint64_t* st_len) {
+    return analyse_host(n, row_ptr, col_idx, leaf, nullptr, 0, perm, nodes, cap, n_nodes, st, st_cap, st_len);
+}
+
+// the analysis with `last` as the root's own (nd.hpp); an index >= n or a repeated one: BSM_ERR_INVALID
+extern "C" int bsm_nd_analyse_last(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
+                                   const uint64_t* last, uint64_t m, int64_t* perm, int64_t* nodes, uint64_t cap,
+                                   uint64_t* n_nodes, int64_t* st, uint64_t st_cap, uint64_t* st_len) {
+    return analyse_host(n, row_ptr, col_idx, leaf, last, m, perm, nodes, cap, n_nodes, st, st_cap, st_len);
 }

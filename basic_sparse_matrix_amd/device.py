@@ -240,6 +240,80 @@ def nd_factor_solve_sparse(factor, b, rows=None, out: torch.Tensor | None = None
     return out
 
 
+def _schur_operand(what: str, name: str, t: torch.Tensor, factor, rows: int) -> int:
+    """The checks of a (rows,) or row-major (rows, k) device operand; returns k."""
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    if t.dtype != want:
+        raise TypeError(f"{what}: {name} is {t.dtype}, the factor is {factor.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} is not on the device")
+    if t.dim() not in (1, 2) or t.shape[0] != rows or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous, ({rows},) or ({rows}, k), got {tuple(t.shape)}")
+    return t.shape[1] if t.dim() == 2 else 1
+
+
+def nd_factor_schur(factor, a, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
+    """``NdFactor.schur`` with ``S`` resident in HBM (``bsm_dev_nd_factor_schur``):
+    ``a`` is the host ``Csr`` the factor was made of, ``out`` an ``(m, m)``
+    contiguous tensor of the factor's dtype on its device (``S`` is exactly
+    symmetric, so row- and column-major agree) and defaults to a new one. Runs
+    on ``stream`` and returns after it has drained; the same kernel and bits
+    as the host call."""
+    from .sparse import _raise_for
+
+    h = factor._h()
+    m = factor._schur_m("schur")
+    want = TORCH_DT[np.dtype(factor.dtype)]
+    out = torch.empty((m, m), dtype=want, device="cuda") if out is None else out
+    if out.dtype != want:
+        raise TypeError(f"nd_factor_schur: out is {out.dtype}, the factor is {factor.dtype}")
+    if not out.is_cuda:
+        raise ValueError("nd_factor_schur: out is not on the device")
+    if tuple(out.shape) != (m, m) or not out.is_contiguous():
+        raise ValueError(f"nd_factor_schur: out must be contiguous, ({m}, {m}), got {tuple(out.shape)}")
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_schur(h, a._device().handle, out.data_ptr(), max(m, 1),
+                                                             _stream(stream)))
+    return out
+
+
+def nd_factor_schur_condense(factor, b: torch.Tensor, out: torch.Tensor | None = None, *, stream=None) -> torch.Tensor:
+    """``NdFactor.schur_condense`` on device tensors
+    (``bsm_dev_nd_factor_schur_condense``): ``b`` is ``(n,)`` or row-major
+    ``(n, k)``, ``out`` ``(m,)`` / ``(m, k)`` in ``schur_index``'s order, both
+    contiguous, of the factor's dtype, on its device."""
+    from .sparse import _raise_for
+
+    h = factor._h()
+    m = factor._schur_m("schur_condense")
+    k = _schur_operand("nd_factor_schur_condense", "b", b, factor, factor.n)
+    out = torch.empty((m,) + tuple(b.shape[1:]), dtype=b.dtype, device=b.device) if out is None else out
+    if _schur_operand("nd_factor_schur_condense", "out", out, factor, m) != k or out.dim() != b.dim():
+        raise ValueError(f"nd_factor_schur_condense: out is {tuple(out.shape)}, b {tuple(b.shape)}")
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_schur_condense(h, _p(b), k, _p(out), _stream(stream)))
+    return out
+
+
+def nd_factor_schur_expand(factor, b: torch.Tensor, xg: torch.Tensor, out: torch.Tensor | None = None, *,
+                           stream=None) -> torch.Tensor:
+    """``NdFactor.schur_expand`` on device tensors
+    (``bsm_dev_nd_factor_schur_expand``): ``b`` and ``out`` ``(n,)`` or
+    row-major ``(n, k)``, ``xg`` ``(m,)`` / ``(m, k)`` in ``schur_index``'s
+    order; ``out`` defaults to a new tensor and may be ``b``."""
+    from .sparse import _raise_for
+
+    h = factor._h()
+    m = factor._schur_m("schur_expand")
+    what = "nd_factor_schur_expand"
+    k = _schur_operand(what, "b", b, factor, factor.n)
+    out = torch.empty_like(b) if out is None else out
+    if _schur_operand(what, "xg", xg, factor, m) != k or xg.dim() != b.dim():
+        raise ValueError(f"{what}: xg is {tuple(xg.shape)}, b {tuple(b.shape)}")
+    if _schur_operand(what, "out", out, factor, factor.n) != k or out.shape != b.shape:
+        raise ValueError(f"{what}: out is {tuple(out.shape)}, b {tuple(b.shape)}")
+    _raise_for(_lib.require_device().bsm_dev_nd_factor_schur_expand(h, _p(b), k, _p(xg), _p(out), _stream(stream)))
+    return out
+
+
 def nd_factor_solve_refined(factor, a, b: torch.Tensor, out: torch.Tensor | None = None, *, max_iter: int = 5,
                             tol: float | None = None, stream=None):
     """``NdFactor.solve_refined`` with ``b`` and ``x`` resident in HBM

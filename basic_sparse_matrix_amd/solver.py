@@ -269,7 +269,9 @@ class NdFactor:
     dtype may be chosen apart from the matrix's
     (``cholesky_nd(a, factor_dtype=...)``). ``refactor_values`` refactors from
     a device tensor of values, and ``autograd.nd_solve`` / ``autograd.nd_logdet``
-    differentiate the solve and the log-determinant. The handle owns its
+    differentiate the solve and the log-determinant. A factor made with
+    ``cholesky_nd(a, schur=idx)`` also gives the Schur complement on those
+    vertices (``schur``, ``schur_condense``, ``schur_expand``). The handle owns its
     numeric storage (``nbytes``; ~5.6 GB at C5 in f64) until ``close()``, the
     end of a ``with`` block, or garbage collection. This build's addition."""
 
@@ -691,6 +693,91 @@ class NdFactor:
         out, _ = self._solve_sparse(k, col_ptr, c, np.ones(k, dtype=self.dtype), r)
         return np.stack(out, axis=1) if k else np.zeros((r.shape[0], 0), dtype=self.dtype)
 
+    @property
+    def schur_index(self) -> np.ndarray:
+        """The Schur set as given to ``cholesky_nd(a, schur=idx)`` (uint64; empty
+        for a factor made without one): the order of ``schur``'s rows and
+        columns and of ``schur_condense``'s. ``perm`` ends in it, sorted."""
+        lib = _lib.load()
+        m = ctypes.c_uint64()
+        _lib.check(lib.bsm_nd_factor_schur_info(self._h(), ctypes.byref(m), None))
+        idx = np.zeros(m.value, dtype=np.uint64)
+        _lib.check(lib.bsm_nd_factor_schur_info(self._h(), None, _lib.ptr(idx)))
+        return idx
+
+    def _schur_m(self, what: str) -> int:
+        m = self.schur_index.shape[0]
+        if m == 0:  # the library's own refusal, before the shapes are compared with an empty set's
+            raise _lib.BsmError(_lib.BSM_ERR_INVALID, f"nd factor {what}: the factor was made without a Schur set "
+                                                      "(cholesky_nd(a, schur=idx))")
+        return m
+
+    def _dense_cols(self, what: str, d: Dense, rows: int) -> tuple[int, list]:
+        dims = d.get_dims()
+        k = dims.cols
+        if k and d.dtype != self.dtype:
+            raise TypeError(f"NdFactor.{what}: needs Dense<{self.dtype}>, got {d.dtype}")
+        if dims.rows != rows:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        return k, [np.ascontiguousarray(np.asarray(d.get_col(j))[:rows]) for j in range(k)]
+
+    def schur(self, a: Csr) -> np.ndarray:
+        """``S = A_GG - A_GI A_II^-1 A_IG`` on the set ``G`` the factor was made
+        with (``bsm_nd_factor_schur``), an ``(m, m)`` array of the factor's
+        dtype with rows and columns in ``schur_index``'s order. ``a`` is the
+        matrix this is the factor of (its pattern is checked as ``refactor``
+        checks it; its values are the caller's responsibility). ``S`` is read
+        out of the factorisation: ``a``'s entries inside ``G`` plus the update
+        block left under the separator tree's root, one addition per entry in
+        a fixed order. ``S == S.T`` exactly and the bits repeat. Raises for a
+        factor made without a set, and after ``update`` / ``downdate`` until a
+        ``refactor``."""
+        _check_factorable(a, "NdFactor.schur")
+        h = self._h()
+        m = self._schur_m("schur")
+        out = np.zeros((m, m), dtype=self.dtype, order="F")
+        _raise_for(_lib.require_device().bsm_nd_factor_schur(h, a._device().handle, _lib.ptr(out), max(m, 1)))
+        return out
+
+    def schur_condense(self, b: Dense) -> Dense:
+        """``g = b_G - A_GI A_II^-1 b_I`` for the columns of ``b`` (``n x k``,
+        the factor's dtype): a ``Dense`` ``m x k`` in ``schur_index``'s order
+        (``bsm_nd_factor_schur_condense``). With ``S x_G = g`` solved by the
+        caller, :meth:`schur_expand` gives ``x``."""
+        h = self._h()
+        m = self._schur_m("schur_condense")
+        k, b_cols = self._dense_cols("schur_condense", b, self.n)
+        out = Dense.new_default_with_dims(k, m, dtype=self.dtype)
+        _raise_for(_lib.require_device().bsm_nd_factor_schur_condense(h, _lib.ptr_array(b_cols), k,
+                                                                      _lib.ptr_array(out.data)))
+        return out
+
+    def schur_expand(self, b: Dense, xg) -> Dense:
+        """``x`` (``n x k``) from ``b`` and a given ``x_G`` (``xg``: a ``Dense``
+        or array ``m x k`` of the factor's dtype, ``schur_index``'s order):
+        ``x_I = A_II^-1 (b_I - A_IG x_G)`` (``bsm_nd_factor_schur_expand``).
+        Stateless: it repeats ``schur_condense``'s forward pass and keeps
+        nothing between the two calls (about one forward pass of a solve).
+        With ``xg`` the rows ``schur_index`` of ``solve(b)`` it returns
+        ``solve(b)`` bit for bit."""
+        h = self._h()
+        m = self._schur_m("schur_expand")
+        k, b_cols = self._dense_cols("schur_expand", b, self.n)
+        if not isinstance(xg, Dense):
+            arr = np.asarray(xg)
+            arr = arr.reshape(arr.shape[0], -1) if arr.ndim <= 2 else arr
+            if arr.ndim != 2:
+                raise ValueError(f"NdFactor.schur_expand: xg must be (m,) or (m, k), got {arr.shape}")
+            xg = Dense.from_columns([np.ascontiguousarray(arr[:, j]) for j in range(arr.shape[1])]) \
+                if arr.shape[1] else Dense(0, arr.shape[0], [])
+        kg, g_cols = self._dense_cols("schur_expand", xg, m)
+        if kg != k:
+            raise MatErr(MatErrKind.IncorrectDimensions)
+        out = Dense.new_default_with_dims(k, self.n, dtype=self.dtype)
+        _raise_for(_lib.require_device().bsm_nd_factor_schur_expand(h, _lib.ptr_array(b_cols), k,
+                                                                    _lib.ptr_array(g_cols), _lib.ptr_array(out.data)))
+        return out
+
     def logdet(self) -> float:
         """``log det A = 2 sum log L_ii`` (``bsm_nd_factor_logdet``), summed in
         f64 in a fixed order: the same bits on every call."""
@@ -813,7 +900,7 @@ class NdFactor:
         self.close()
 
 
-def cholesky_nd(a: Csr, factor_dtype=None) -> NdFactor:
+def cholesky_nd(a: Csr, factor_dtype=None, schur=None) -> NdFactor:
     """Analysis (through the plan caches of ``solve(order="nd")``) and numeric
     factorisation of ``P A P^T`` (``bsm_nd_factor_create``), kept as an
     :class:`NdFactor`. The same type and shape checks as :func:`solve`; a
@@ -823,14 +910,30 @@ def cholesky_nd(a: Csr, factor_dtype=None) -> NdFactor:
     chooses the dtype the factor is computed and stored in
     (``bsm_nd_factor_create_as``): an f32 factor of an f64 matrix has half the
     bytes and the bits of ``cholesky_nd`` on the matrix rounded to f32;
-    ``NdFactor.solve_refined`` brings its solves back to f64 accuracy."""
+    ``NdFactor.solve_refined`` brings its solves back to f64 accuracy.
+
+    ``schur`` (a 1-D integer array-like of distinct vertices, any order;
+    ``None`` = none): the Schur set ``G`` (``bsm_nd_factor_create_schur``). The
+    analysis orders these vertices last, as the separator tree's root, over the
+    ordinary tree of the others, and the factor then also answers
+    ``schur(a)``, ``schur_condense(b)`` and ``schur_expand(b, xg)``. Every
+    other method works as on any factor (of ``P A P^T`` with this ``P``), and
+    ``refactor`` / ``refactor_partial`` keep the set. Such a plan is the
+    factor's alone: the plan caches neither hold it nor hand it out. An index
+    ``>= n`` or a repeated one raises the error for ``BSM_ERR_INVALID``, more
+    than 16384 vertices the one for ``BSM_ERR_UNSUPPORTED`` (the root front is
+    dense, ``(64 ceil(m / 64))^2`` values)."""
     _check_factorable(a, "cholesky_nd")
     if factor_dtype is not None and np.dtype(factor_dtype) not in _FLOATS:
         raise TypeError(f"cholesky_nd: factor_dtype must be float32 or float64, got {np.dtype(factor_dtype)}")
+    idx = None if schur is None else NdFactor._rows_arg("cholesky_nd", "schur", schur)
     dev = a._device()
     lib = _lib.require_device()
     out = ctypes.c_void_p()
-    if factor_dtype is None:
+    if idx is not None:
+        code = _lib.DTYPE_CODES[a.dtype if factor_dtype is None else np.dtype(factor_dtype)]
+        _raise_for(lib.bsm_nd_factor_create_schur(dev.handle, code, _lib.ptr(idx), idx.shape[0], ctypes.byref(out)))
+    elif factor_dtype is None:
         _raise_for(lib.bsm_nd_factor_create(dev.handle, ctypes.byref(out)))
     else:
         _raise_for(lib.bsm_nd_factor_create_as(dev.handle, _lib.DTYPE_CODES[np.dtype(factor_dtype)],
@@ -838,23 +941,32 @@ def cholesky_nd(a: Csr, factor_dtype=None) -> NdFactor:
     return NdFactor(out.value, a.dtype)
 
 
-def nd_analyse(n: int, row_ptr, col_idx, leaf: int = 256) -> dict:
+def nd_analyse(n: int, row_ptr, col_idx, leaf: int = 256, last=None) -> dict:
     """The host analysis of ``solve(order="nd")`` on a CSR pattern
     (``bsm_nd_analyse``; no device): ``perm`` (perm[new] = old) and the
     separator tree in post-order (``start``, ``end``, ``parent``, ``level``,
-    ``slot``, front rows ``st``)."""
+    ``slot``, front rows ``st``). ``last`` (distinct vertices, any order;
+    ``bsm_nd_analyse_last``): the root node owns exactly these, over the tree
+    of the others, as ``cholesky_nd(a, schur=last)`` orders them."""
     lib = _lib.load()
     rp = np.ascontiguousarray(row_ptr, dtype=np.uint64)
     ci = np.ascontiguousarray(col_idx, dtype=np.uint64)
     perm = np.zeros(n, dtype=np.int64)
     nn = ctypes.c_uint64(0)
     sl = ctypes.c_uint64(0)
-    _lib.check(lib.bsm_nd_analyse(n, _lib.ptr(rp), _lib.ptr(ci), leaf, _lib.ptr(perm), None, 0, ctypes.byref(nn),
-                                  None, 0, ctypes.byref(sl)))
+    if last is None:
+        def run(*out):
+            return lib.bsm_nd_analyse(n, _lib.ptr(rp), _lib.ptr(ci), leaf, *out)
+    else:
+        lv = np.ascontiguousarray(last, dtype=np.uint64)
+
+        def run(*out):
+            return lib.bsm_nd_analyse_last(n, _lib.ptr(rp), _lib.ptr(ci), leaf, _lib.ptr(lv), lv.shape[0], *out)
+    _lib.check(run(_lib.ptr(perm), None, 0, ctypes.byref(nn), None, 0, ctypes.byref(sl)))
     nodes = np.zeros((max(nn.value, 1), 8), dtype=np.int64)
     st = np.zeros(max(sl.value, 1), dtype=np.int64)
-    _lib.check(lib.bsm_nd_analyse(n, _lib.ptr(rp), _lib.ptr(ci), leaf, _lib.ptr(perm), _lib.ptr(nodes), nn.value,
-                                  ctypes.byref(nn), _lib.ptr(st), sl.value, ctypes.byref(sl)))
+    _lib.check(run(_lib.ptr(perm), _lib.ptr(nodes), nn.value, ctypes.byref(nn), _lib.ptr(st), sl.value,
+                   ctypes.byref(sl)))
     nodes = nodes[: nn.value]
     return {"perm": perm, "start": nodes[:, 0], "end": nodes[:, 1], "parent": nodes[:, 2], "level": nodes[:, 3],
             "slot": nodes[:, 4],

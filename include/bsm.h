@@ -600,6 +600,54 @@ int bsm_solve_nd(const bsm_csr* a, uint64_t k, uint64_t n, const void* const* b_
  *    pattern, are compared on the device, and every stored entry with
  *    col <= row whose bits differ (so NaN and -0 count) is a changed place.
  *    info[2] is their number. No differing entry: the factor's bits stay.
+ *  - bsm_nd_factor_create_schur: bsm_nd_factor_create_as with a Schur set G:
+ *    m distinct vertices idx (A's order, any order among themselves) that the
+ *    analysis orders LAST, as the separator tree's root front's own columns
+ *    (perm[n - m .. n) = sorted idx); under that root is the ordinary tree of
+ *    the other vertices I. The handle is a factor like any other, of P A P^T
+ *    with this P: every other call works on it unchanged, and the refactor
+ *    calls keep the set. Its plan is the handle's alone, never in the plan
+ *    caches. m == 0 gives bsm_nd_factor_create_as's factor (no set). Errors,
+ *    before any device is asked for: a null a, out or (m > 0) idx, a
+ *    factor_dtype that is no float -> BSM_ERR_INVALID; an index >= n, then a
+ *    repeated index -> BSM_ERR_INVALID (naming the entry); m > 16384 ->
+ *    BSM_ERR_UNSUPPORTED (the root front is dense: (64 ceil(m / 64))^2 values).
+ *  - bsm_nd_factor_schur_info: *m and the set as given (idx_out: m entries).
+ *    Any pointer may be NULL; m is 0 for a factor made without a set.
+ *  - bsm_nd_factor_schur: S = A_GG - A_GI A_II^-1 A_IG into out (host), m x m
+ *    of the FACTOR's dtype, column-major with leading dimension ld >= m, rows
+ *    and columns in the order idx was given. a is the matrix the handle is
+ *    the factor of: its pattern is checked as bsm_nd_factor_refactor checks it
+ *    (with its errors); its VALUES are the caller's responsibility, as in
+ *    bsm_nd_factor_solve_refined. Entry (i, j) is a's stored lower entry
+ *    between the two vertices (converted to the factor's dtype as the factor's
+ *    input is; 0 if none) plus the update-block entry the factorisation left
+ *    under the root: one addition, in that order, no atomics; S is exactly
+ *    symmetric, the same call gives the same bits, and another order of idx
+ *    gives the same values permuted. The root's own L is not read.
+ *  - bsm_nd_factor_schur_condense: g = b_G - A_GI A_II^-1 b_I for k columns:
+ *    b_cols are k host columns of n values, g_cols k host columns of m (the
+ *    order of idx), all of the factor's dtype. The solve's forward levels
+ *    below the root, then the root's own gather of b and its child's update
+ *    vector.
+ *  - bsm_nd_factor_schur_expand: x from b and a given x_G (x_gamma_cols: k
+ *    host columns of m, the order of idx; x_cols: k columns of n): the same
+ *    forward levels, x_G put where the root's backward step leaves its x, the
+ *    backward levels below the root, the scatter. STATELESS: it repeats the
+ *    forward pass and keeps nothing between the two calls. With x_G the rows
+ *    idx of bsm_nd_factor_solve's x it returns that x bit for bit.
+ *    With S x_G = g solved by the caller, condense + expand is a solve.
+ *  - bsm_dev_nd_factor_schur / _schur_condense / _schur_expand: the same with
+ *    out (column-major, ld), b / x (ROW-major n x k) and g / x_gamma (ROW-major
+ *    m x k) in HBM on the factor's device; they run on `stream` and return
+ *    after it has drained.
+ *    The three calls refuse: a null handle or buffer, a factor made without a
+ *    set, ld < m -> BSM_ERR_INVALID (no device asked for); another device, a
+ *    handle without values -> BSM_ERR_INVALID; a handle on which an update or
+ *    downdate has run since its last factorisation -> BSM_ERR_UNSUPPORTED
+ *    (refactor first: the update blocks are stale). Both pipelines
+ *    (BSM_ND_PLAIN=1 too) leave the update blocks in place and are supported.
+ *    They take the handle's mutex. This build's addition.
  * A factor is used on the device it was made on (else BSM_ERR_INVALID). */
 typedef struct bsm_nd_factor bsm_nd_factor;
 #define BSM_ND_SYS_A 0  /* A x = b (b and x in A's order) */
@@ -655,6 +703,17 @@ int bsm_dev_nd_factor_solve_sparse(const bsm_nd_factor* f, uint64_t k, const uin
 int bsm_nd_factor_refactor_partial(bsm_nd_factor* f, const bsm_csr* a, uint64_t nc, const uint64_t* rows,
                                    const uint64_t* cols, uint64_t* info);
 int bsm_nd_factor_refactor_since(bsm_nd_factor* f, const bsm_csr* a_old, const bsm_csr* a_new, uint64_t* info);
+int bsm_nd_factor_create_schur(const bsm_csr* a, int factor_dtype, const uint64_t* idx, uint64_t m,
+                               bsm_nd_factor** out);
+int bsm_nd_factor_schur_info(const bsm_nd_factor* f, uint64_t* m, uint64_t* idx_out);
+int bsm_nd_factor_schur(const bsm_nd_factor* f, const bsm_csr* a, void* out, uint64_t ld);
+int bsm_dev_nd_factor_schur(const bsm_nd_factor* f, const bsm_csr* a, void* out, uint64_t ld, void* stream);
+int bsm_nd_factor_schur_condense(const bsm_nd_factor* f, const void* const* b_cols, uint64_t k, void* const* g_cols);
+int bsm_nd_factor_schur_expand(const bsm_nd_factor* f, const void* const* b_cols, uint64_t k,
+                               const void* const* x_gamma_cols, void* const* x_cols);
+int bsm_dev_nd_factor_schur_condense(const bsm_nd_factor* f, const void* b, uint64_t k, void* g, void* stream);
+int bsm_dev_nd_factor_schur_expand(const bsm_nd_factor* f, const void* b, uint64_t k, const void* x_gamma, void* x,
+                                   void* stream);
 void bsm_nd_factor_free(bsm_nd_factor* f);
 /* The differentiable solve's pieces: everything a gradient of x = S^-1 b or of
  * log det S with respect to the stored values needs, with every operand in HBM
@@ -704,6 +763,14 @@ int bsm_nd_cache_info(uint64_t* entries, uint64_t* kept_bytes, uint64_t* hits, u
 int bsm_nd_analyse(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
                    int64_t* perm, int64_t* nodes, uint64_t cap, uint64_t* n_nodes, int64_t* st,
                    uint64_t st_cap, uint64_t* st_len);
+/* The same with the m distinct vertices `last` ordered last, as the root node's
+ * own (bsm_nd_factor_create_schur's analysis): the last node owns [n - m, n),
+ * perm[n - m .. n) is `last` sorted, and its one child is the tree of the
+ * other vertices. m == 0: bsm_nd_analyse's arrays. An index >= n or a repeated
+ * one -> BSM_ERR_INVALID, m > 16384 -> BSM_ERR_UNSUPPORTED. */
+int bsm_nd_analyse_last(uint64_t n, const uint64_t* row_ptr, const uint64_t* col_idx, uint64_t leaf,
+                        const uint64_t* last, uint64_t m, int64_t* perm, int64_t* nodes, uint64_t cap,
+                        uint64_t* n_nodes, int64_t* st, uint64_t st_cap, uint64_t* st_len);
 
 /* ---- device-level entry points (HBM pointers, async on `stream`) --------- */
 /* Synthetic CSR generator (bsm_synth.h recipe): rows [row0, row0+rows) of a

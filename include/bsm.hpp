@@ -857,6 +857,81 @@ public:
         return out;
     }
 
+    /// The factor in dtype T of `a` with the Schur set `idx` (bsm_nd_factor_create_schur; see cholesky_nd_schur):
+    /// distinct vertices, any order, which the analysis orders last as the separator tree's root. An index >= n,
+    /// a repeated one or more than 16384 of them throw.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    static NdFactor with_schur(const Csr<U>& a, const std::vector<uint64_t>& idx) {
+        if (a.get_dims().rows != a.get_dims().cols)
+            throw Panic("called `Result::unwrap()` on an `Err` value: NonSquareMatrix");
+        auto h = a.device();
+        bsm_nd_factor* f = nullptr;
+        detail::check(bsm_nd_factor_create_schur(h.get(), detail::dtype_of<T>::value, idx.data(), idx.size(), &f));
+        NdFactor out;
+        out.f_.reset(f);
+        detail::check(bsm_nd_factor_info(f, &out.n_, nullptr, nullptr, nullptr));
+        out.src_dtype_ = detail::dtype_of<U>::value;
+        return out;
+    }
+
+    /// The Schur set as given (empty: the factor was made without one): the order of schur()'s rows and columns.
+    std::vector<uint64_t> schur_index() const {
+        uint64_t m = 0;
+        detail::check(bsm_nd_factor_schur_info(f_.get(), &m, nullptr));
+        std::vector<uint64_t> idx(m);
+        detail::check(bsm_nd_factor_schur_info(f_.get(), nullptr, idx.data()));
+        return idx;
+    }
+
+    /// S = A_GG - A_GI A_II^-1 A_IG on the set G (bsm_nd_factor_schur): m x m, column-major, in schur_index()'s
+    /// order; exactly symmetric. `a` is the matrix this is the factor of (its pattern is checked, its values are
+    /// the caller's responsibility). Throws for a factor made without a set, and after update / downdate until a
+    /// refactor.
+    template <class U>
+        requires std::is_floating_point_v<U>
+    std::vector<T> schur(const Csr<U>& a) const {
+        const size_t m = schur_index().size();
+        std::vector<T> out(m * m);
+        auto h = a.device();
+        detail::check(bsm_nd_factor_schur(f_.get(), h.get(), out.data(), m ? m : 1));
+        return out;
+    }
+
+    /// g = b_G - A_GI A_II^-1 b_I (bsm_nd_factor_schur_condense): m x k in schur_index()'s order.
+    Dense<T> schur_condense(const Dense<T>& b) const {
+        if (b.get_dims().rows != n_) throw Panic("NdFactor::schur_condense: IncorrectDimensions");
+        const size_t k = b.get_dims().cols, m = schur_index().size();
+        Dense<T> out = Dense<T>::new_default_with_dims(k, m);
+        std::vector<const void*> bc(k);
+        std::vector<void*> gc(k);
+        for (size_t j = 0; j < k; ++j) {
+            bc[j] = b.get_col(j).data();
+            gc[j] = out.get_col_mut(j).data();
+        }
+        detail::check(bsm_nd_factor_schur_condense(f_.get(), bc.data(), k, gc.data()));
+        return out;
+    }
+
+    /// x from b and a given x_G (bsm_nd_factor_schur_expand; xg: m x k in schur_index()'s order). Stateless: it
+    /// repeats schur_condense's forward pass. With xg the rows schur_index() of solve(b) it returns solve(b) bit
+    /// for bit.
+    Dense<T> schur_expand(const Dense<T>& b, const Dense<T>& xg) const {
+        const size_t k = b.get_dims().cols;
+        if (b.get_dims().rows != n_ || xg.get_dims().cols != k || xg.get_dims().rows != schur_index().size())
+            throw Panic("NdFactor::schur_expand: IncorrectDimensions");
+        Dense<T> out = Dense<T>::new_default_with_dims(k, n_);
+        std::vector<const void*> bc(k), gc(k);
+        std::vector<void*> xc(k);
+        for (size_t j = 0; j < k; ++j) {
+            bc[j] = b.get_col(j).data();
+            gc[j] = xg.get_col(j).data();
+            xc[j] = out.get_col_mut(j).data();
+        }
+        detail::check(bsm_nd_factor_schur_expand(f_.get(), bc.data(), k, gc.data(), xc.data()));
+        return out;
+    }
+
     size_t rows() const { return n_; }
 
     /// New values on the same pattern (bsm_nd_factor_refactor): afterwards the
@@ -1235,6 +1310,15 @@ template <class F, class T>
     requires std::is_floating_point_v<F> && std::is_floating_point_v<T>
 NdFactor<F> cholesky_nd_as(const Csr<T>& a) {
     return NdFactor<F>::from_matrix_of(a);
+}
+
+/// The nd factor of `a` in dtype F with the Schur set `idx` (this build's addition): NdFactor::schur,
+/// schur_condense and schur_expand then give the Schur complement on those vertices, its right-hand side and the
+/// expansion of its solution; every other method works as on any factor, and refactor keeps the set.
+template <class F, class T>
+    requires std::is_floating_point_v<F> && std::is_floating_point_v<T>
+NdFactor<F> cholesky_nd_schur(const Csr<T>& a, const std::vector<uint64_t>& idx) {
+    return NdFactor<F>::with_schur(a, idx);
 }
 
 }  // namespace bsm

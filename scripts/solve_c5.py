@@ -184,6 +184,11 @@ def main():
                     help="only the differentiable solve's record: refactor_values against refactor, and for each K "
                          "the solve, the backward's solve, nd_factor_sddmm (with its achieved bytes per second) and "
                          "inv_pattern, operands in HBM (profiles/nd_grad_c5.jsonl)")
+    ap.add_argument("--schur", type=int, default=None, metavar="LINE",
+                    help="only the Schur complement's record, the set being grid line LINE (m = g): cholesky_nd and "
+                         "refactor with and without the set, schur (with the gather kernel's bytes and its share of "
+                         "the HBM peak), schur_condense / schur_expand / solve for k = 1 and 32, and inv_block on the "
+                         "set (profiles/nd_schur_c5.jsonl)")
     ap.add_argument("--mass", choices=("none", "lumped", "consistent"), default=None,
                     help="with --eig: the generalised problem's mass matrix, block 4 (profiles/nd_eig_gen_c5.jsonl). "
                          "lumped: a diagonal hashed into [0.5, 2); consistent: the 9-point kron(M1, M1), M1 = "
@@ -227,6 +232,14 @@ def main():
             for line in nd_grad_ops(A, [int(k) for k in args.grad.split(",")], (n, rp, ci, v)):
                 print(json.dumps(line), flush=True)
                 out.write(json.dumps(line) + "\n")
+        return
+    if args.schur is not None:
+        _lib.stage_timing(True)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        line = nd_schur_ops(A, g, args.schur, (n, rp, ci, v))
+        print(json.dumps(line), flush=True)
+        with open(os.path.join(ROOT, "profiles", "nd_schur_c5.jsonl"), "a") as out:
+            out.write(json.dumps(line) + "\n")
         return
     if args.eig:
         _lib.stage_timing(True)
@@ -669,6 +682,93 @@ def nd_updown_ops(A, B, ks, reps, pattern):
             f.refactor(A)
             lines.append(line)
     return lines
+
+
+HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E, the vendor's figure; a float4 copy reaches 6.29e12 of it
+
+
+def nd_schur_ops(A, g, line, pattern):
+    """The Schur complement on grid line `line` (m = g vertices) of the kept
+    factor: host wall ms around synchronous calls, medians of 6 after a
+    warm-up pair, all in one session, operands of the solves in HBM. create:
+    cholesky_nd on a fresh handle of the pattern (without the set the first is
+    the cold analysis and the later ones take the plan from the cache; with
+    the set every call analyses: the plan is the factor's alone). The gather
+    kernel's bytes are counted from the shapes: the child's update block's
+    lower 64 x 64 tiles read once, S written once."""
+    import torch
+
+    from basic_sparse_matrix_amd import cholesky_nd, device
+
+    n, rp, ci, v = pattern
+    dt = A.dtype
+    es = np.dtype(dt).itemsize
+    idx = line * g + np.arange(g)
+    m = len(idx)
+    med = lambda t: round(1e3 * float(np.median(t)), 3)  # noqa: E731
+    fresh = lambda: Csr.from_csr_arrays((n, n), rp, ci, v)  # noqa: E731
+
+    def clock(fn, warm=2, reps=6):
+        t = []
+        for _ in range(warm + reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            t.append(time.perf_counter() - t0)
+        return t[warm:]
+
+    out = {"metric": "C5 nd factor: Schur complement on a grid line (host wall ms, medians of 6 after a warm-up pair)",
+           "n": n, "m": m, "line": line, "dtype": np.dtype(dt).name}
+    create = {}
+    for name, sch in (("plain", None), ("schur", idx)):
+        _lib.nd_cache_clear()
+        t = []
+        for _ in range(4):
+            a = fresh()
+            a._device()
+            t0 = time.perf_counter()
+            f = cholesky_nd(a, schur=sch)
+            t.append(time.perf_counter() - t0)
+            f.close()
+        create[name] = {"first_ms": round(1e3 * t[0], 2), "later_ms": med(t[1:])}
+    out["cholesky_nd_ms"] = create
+    rng = np.random.default_rng(77)
+    with cholesky_nd(A) as fp, cholesky_nd(A, schur=idx) as fs:
+        out["factor_bytes"] = {"plain": fp.nbytes, "schur": fs.nbytes}
+        out["refactor_ms"] = {"plain": med(clock(lambda: fp.refactor(A))), "schur": med(clock(lambda: fs.refactor(A)))}
+        S_dev = torch.empty((m, m), dtype=device.TORCH_DT[np.dtype(dt)], device="cuda")
+        st = []
+
+        def gather():
+            device.nd_factor_schur(fs, A, out=S_dev)
+            st.append(_lib.stage_times().get("nd_schur_gather", 0.0))
+
+        t = clock(gather)
+        nt = (m + 63) // 64
+        nbytes = (nt * (nt + 1) // 2) * 4096 * es + m * m * es
+        kernel_ms = float(np.median(st[2:]))
+        out["schur"] = {"call_ms": med(t), "host_copy_call_ms": med(clock(lambda: fs.schur(A))),
+                        "gather_device_ms": round(kernel_ms, 4), "gather_bytes": nbytes,
+                        "gather_bytes_per_s": round(nbytes / (kernel_ms * 1e-3), 0) if kernel_ms > 0 else None,
+                        "share_of_hbm_peak": round(nbytes / (kernel_ms * 1e-3) / HBM_PEAK_BYTES_PER_S, 4)
+                        if kernel_ms > 0 else None}
+        S = S_dev.cpu().numpy().astype(np.float64)
+        for k in (1, 32):
+            b = torch.from_numpy(rng.uniform(-1.0, 1.0, (n, k)).astype(dt)).cuda()
+            x = device.nd_factor_solve(fs, b)
+            gk = device.nd_factor_schur_condense(fs, b)
+            xg = torch.from_numpy(np.linalg.solve(S, gk.cpu().numpy().astype(np.float64)).astype(dt)).cuda()
+            xe = device.nd_factor_schur_expand(fs, b, xg)
+            err = float((xe - x).abs().max() / x.abs().max())
+            out[f"k{k}"] = {"solve_ms": med(clock(lambda: device.nd_factor_solve(fs, b))),
+                            "solve_plain_factor_ms": med(clock(lambda: device.nd_factor_solve(fp, b))),
+                            "schur_condense_ms": med(clock(lambda: device.nd_factor_schur_condense(fs, b))),
+                            "schur_expand_ms": med(clock(lambda: device.nd_factor_schur_expand(fs, b, xg))),
+                            "condense_solve_expand_vs_solve_max_rel": err}
+        # the only way to comparable information without the set: |G| solves for A^-1[G, G] (then a dense inverse)
+        out["inv_block_ms"] = med(clock(lambda: fp.inv_block(idx, idx), warm=1, reps=3))
+    return out
 
 
 def nd_sparse_rhs_ops(A, B, reps, pattern):
