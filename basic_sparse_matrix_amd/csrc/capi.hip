@@ -987,7 +987,11 @@ int bsm_csr_mul_sparse(const bsm_csr* a, const bsm_csr* b, bsm_csr** out) {
 int bsm_csr_transpose(const bsm_csr* a, bsm_csr** out) {
     BSM_REQUIRE(a && out, BSM_ERR_INVALID, "null argument");
     hipStream_t s;
-    BSM_TRY(ctx_stream(&s));
+    BSM_TRY(ctx_stream(&s));  // the device is asked for before the handle is read
+    // the public operation only: the internal transposes (mul_vector's row sort, the solvers) keep theirs
+    BSM_REQUIRE(a->cols > 0, BSM_ERR_PANIC,
+                "big eek: transpose of a matrix with 0 columns: the result has 0 rows and cannot be finalised "
+                "(sparse.rs:209-211, 317)");
     return transpose_dispatch(a, out, s);
 }
 

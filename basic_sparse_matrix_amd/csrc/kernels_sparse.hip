@@ -1466,6 +1466,13 @@ int sparse_mul_dispatch(const bsm_csr* a, const bsm_csr* b, bsm_csr** out, hipSt
     BSM_REQUIRE(a && b && out, BSM_ERR_INVALID, "null argument");
     BSM_REQUIRE(a->dtype == b->dtype, BSM_ERR_INVALID, "operands have different scalar types");
     const uint64_t rows = a->rows, cols = b->cols;
+    // the reference transposes rhs first (sparse.rs:603), then finalises the result (:634)
+    BSM_REQUIRE(cols > 0, BSM_ERR_PANIC,
+                "big eek: mul_sparse with a rhs of 0 columns: rhs.transpose() finalises a matrix of 0 rows "
+                "(sparse.rs:209-211, 317, 603)");
+    BSM_REQUIRE(rows > 0, BSM_ERR_PANIC,
+                "big eek: mul_sparse on a matrix with 0 rows: the result cannot be finalised "
+                "(sparse.rs:209-211, 634)");
     const unsigned cb = bits_for(cols), rb = bits_for(rows);
     BSM_REQUIRE(cb + rb <= 64 && cb < 64, BSM_ERR_UNSUPPORTED, "mul_sparse: rows x cols too large for 64-bit keys");
     CsrGuard g;

@@ -138,7 +138,8 @@ int bsm_csr_mul_dense(const bsm_csr* a, uint64_t k, uint64_t x_rows, const void*
  * v * rhs[col] in ascending column order, dense output, no zero skip. */
 int bsm_csr_mul_vector(const bsm_csr* a, const void* rhs, uint64_t rhs_len, void* out,
                        uint64_t out_len);
-/* Csr::transpose (sparse.rs:296-318): stable CSR -> CSC. */
+/* Csr::transpose (sparse.rs:296-318): stable CSR -> CSC. 0 columns ->
+ * BSM_ERR_PANIC (the result's finalise panics "big eek", sparse.rs:209-211). */
 int bsm_csr_transpose(const bsm_csr* a, bsm_csr** out);
 /* Csr::add_sparse (sparse.rs:484-540) / Csr::sub_sparse (sparse.rs:542-599):
  * the reference's per-row two-pointer merge over the operands' entries in

@@ -159,3 +159,72 @@ def test_coo_to_csr_vs_oracle(orc, dtype, n, rows, cols):
         coo.insert((a, b, x))
     got = Csr.from_coo(coo)
     assert_csr_bits(got, *orc.csr_from_coo(rows, cols, r, c, v))
+
+
+# ---- the same builders on their size and key-width edges ----------------------
+# coo_keys packs (row << cb) | col like mul_sparse does, cb = bits_for(cols):
+# at dims 2^b + 1 the last row and the last column are the only keys with
+# their field's top bit set. The entry counts below sit on the 256-thread
+# grid and on the 4096-entry scan tile (exclusive_scan_i32_to_i64).
+def coo_of(dims, r, c, v):
+    from basic_sparse_matrix_amd import COO
+
+    coo = COO.with_capacity(dims, len(v), dtype=v.dtype)
+    for a, b, x in zip(r.tolist(), c.tolist(), v):
+        coo.insert((a, b, x))
+    return coo
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int32, np.uint64])
+@pytest.mark.parametrize("rows,cols", [(1, 257), (257, 1), (256, 256), (257, 257), (65537, 65537),
+                                       (2**20 + 1, 2**24 + 1)])
+def test_coo_to_csr_corner_keys(orc, dtype, rows, cols):
+    """300 entries over few rows and columns, the four corners among them,
+    each corner inserted five times with different values (zeros too): the
+    stable order of equal keys decides which come first."""
+    rng = np.random.default_rng([41, rows, cols])
+    some_rows = np.unique(np.concatenate([[0, rows - 1, rows // 2], rng.integers(0, rows, 6)]))
+    some_cols = np.unique(np.concatenate([[0, cols - 1, cols // 2], rng.integers(0, cols, 6)]))
+    n = 300
+    r = some_rows[rng.integers(0, len(some_rows), n)].astype(np.uint64)
+    c = some_cols[rng.integers(0, len(some_cols), n)].astype(np.uint64)
+    v = rng.integers(-4, 5, n).astype(dtype)
+    corners = [(0, 0), (0, cols - 1), (rows - 1, 0), (rows - 1, cols - 1)]
+    at = rng.choice(n, 20, replace=False)
+    for t, i in enumerate(at):
+        r[i], c[i] = corners[t % 4]
+        v[i] = [3, 0, 1, 0, 2][t // 4]
+    got = Csr.from_coo(coo_of((rows, cols), r, c, v))
+    assert got.dims.as_tuple() == (rows, cols)
+    assert_csr_bits(got, *orc.csr_from_coo(rows, cols, r, c, v))
+
+
+def stream_with_kept(rng, n, kept, rows, cols, dtype):
+    """random_stream, then (kept is not None) enough further zeros that exactly
+    `kept` entries survive the zero skip (NaN != 0 survives)."""
+    r, c, v = random_stream(rng, n, rows, cols, dtype)
+    if kept is not None:
+        alive = np.flatnonzero(~(v == 0))
+        v[rng.choice(alive, len(alive) - kept, replace=False)] = 0
+        assert int(np.count_nonzero(~(v == 0))) == kept
+    return r, c, v
+
+
+SIZE_EDGES = [(255, None), (256, None), (257, None), (4095, None), (4096, None), (4097, None), (340, 256),
+              (5400, 4096)]  # the last two: a fifth of the integer stream is zero already
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.int32])
+@pytest.mark.parametrize("n,kept", SIZE_EDGES)
+def test_from_inserts_size_edges(orc, dtype, n, kept):
+    rng = np.random.default_rng([42, n])
+    r, c, v = stream_with_kept(rng, n, kept, 50, 30, dtype)
+    assert_csr_bits(Csr.from_inserts((50, 30), r, c, v), *orc.csr_from_inserts(50, r, c, v))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.int32])
+@pytest.mark.parametrize("n,kept", SIZE_EDGES)
+def test_coo_to_csr_size_edges(orc, dtype, n, kept):
+    rng = np.random.default_rng([43, n])
+    r, c, v = stream_with_kept(rng, n, kept, 300, 70, dtype)
+    assert_csr_bits(Csr.from_coo(coo_of((300, 70), r, c, v)), *orc.csr_from_coo(300, 70, r, c, v))
